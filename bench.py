@@ -10,7 +10,11 @@ configs[1]). With N GPUs every rank decodes its own 2^20-block shard (round-robi
 one N x 2^20-block data set, no collective on the data path): weak scaling, the same bytes per
 GPU at every N.
 
-Also reported:
+A plain run sets up, warms up, times the steps and prints the result line (the metric, its
+ms_per_step and the roofline fraction its kernel time gives). --dump-outputs DIR also writes what
+the last timed step decoded (dump_outputs). Everything below needs --full.
+
+Reported by --full (after validating every decoded block against the generator):
   roofline     algorithmic bytes per step (reads + writes) / kernel time,
                against the 8.0 TB/s HBM peak; `traffic` from rocprof PMC runs (profiles/),
                null when not collected in this process.
@@ -1184,6 +1188,74 @@ def side_config_rate(ctx, config: str, dev, steps: int, warmup: int) -> dict:
     return out
 
 
+def _gather_dev(buf: torch.Tensor, starts: np.ndarray, lens: np.ndarray, dev) -> np.ndarray:
+    """buf[starts[i] : starts[i] + lens[i]] for every i, back to back (indices clamped to buf)."""
+    tot = int(lens.sum())
+    if tot == 0:
+        return buf[:0].cpu().numpy()
+    dpos = np.zeros(len(lens), np.int64)
+    np.cumsum(lens[:-1], out=dpos[1:])
+    t_lens = torch.from_numpy(lens).to(dev)
+    idx = torch.repeat_interleave(torch.from_numpy(starts - dpos).to(dev), t_lens) \
+        + torch.arange(tot, device=dev)
+    return buf[idx.clamp_(0, buf.numel() - 1)].cpu().numpy()
+
+
+def dump_outputs(dirpath: str, cols: SlottedColumns, ext: np.ndarray, dev, seed: int = 20,
+                 data_budget: int = 8 << 20, meta_max: int = 1 << 20) -> list[str]:
+    """What a caller of tpz_decode_blocks holds after the step, as dirpath/<name>.npy, so that two
+    builds can be compared output for output (the inputs are the generator's, seeded):
+      status, count (float32), crc (float64): every block's, or those of a seeded sample of
+        `meta_max` blocks of a larger batch (then their block ids in meta_blocks, float64);
+      sample_blocks (float64): a seeded sample of blocks, chosen from the extents alone, whose
+        encoded bytes add up to at most `data_budget`;
+      ends, keys, values (float32): the sampled blocks' {kend, vend} pairs, key bytes and value
+        bytes back to back in block order, read where the slotted layout (include/tpz_gpu.h)
+        puts them; a block whose status is not OK contributes none.
+    At most 24 B of metadata for each of at most `meta_max` blocks and 4 B per sampled input
+    byte: under 64 MB."""
+    os.makedirs(dirpath, exist_ok=True)
+    nb = len(ext) - 1
+    e = np.asarray(ext, np.uint64).astype(np.int64)
+    blen = e[1:] - e[:-1]
+    rng = np.random.default_rng(seed)
+    meta = np.arange(nb, dtype=np.int64) if nb <= meta_max else \
+        np.sort(rng.choice(nb, meta_max, replace=False)).astype(np.int64)
+    perm = rng.permutation(nb)
+    k = int(np.searchsorted(np.cumsum(blen[perm]), data_budget, side="right"))
+    pick = np.sort(perm[:k]).astype(np.int64)
+    torch.cuda.synchronize(dev)
+    t_meta = torch.from_numpy(meta).to(dev)
+    out = {"meta_blocks": meta.astype(np.float64)} if nb > meta_max else {}
+    out.update({
+        "status": cols.status[t_meta].cpu().numpy().astype(np.float32),
+        "count": cols.count[t_meta].cpu().numpy().astype(np.float32),
+        "crc": cols.crc[t_meta].cpu().numpy().view(np.uint32).astype(np.float64),
+        "sample_blocks": pick.astype(np.float64)})
+    t_pick = torch.from_numpy(pick).to(dev)
+    st = cols.status[t_pick].cpu().numpy()
+    cnt = cols.count[t_pick].cpu().numpy().astype(np.int64)
+    lim = blen[pick]                       # no decoded length exceeds the block's encoded bytes
+    n = np.where(st == _lib.BLOCK_OK, np.clip(cnt, 0, lim), 0)
+    pairs = cols.ends.view(-1, 2)
+    pb = np.asarray(cols.pair_base(e[pick], pick), np.int64)
+    ends = np.stack([_gather_dev(pairs[:, c], pb, n, dev) for c in (0, 1)], axis=1) \
+        if int(n.sum()) else np.zeros((0, 2), np.int32)
+    last = np.cumsum(n) - 1
+    has = n > 0
+    ktot = np.zeros(len(pick), np.int64)
+    vtot = np.zeros(len(pick), np.int64)
+    ktot[has] = np.clip(ends[last[has], 0].astype(np.int64), 0, lim[has])
+    vtot[has] = np.clip(ends[last[has], 1].astype(np.int64), 0, lim[has])
+    kb = _lib.slot_base(e[pick], pick)
+    out["ends"] = ends.astype(np.float32)
+    out["keys"] = _gather_dev(cols.data, kb, ktot, dev).astype(np.float32)
+    out["values"] = _gather_dev(cols.data, kb + _lib.value_start(ktot), vtot, dev).astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return sorted(out)
+
+
 def max_over_ranks(dist, vals, device) -> list[float]:
     """MAX over ranks of the per-rank timings (the only collective; not on the data path)."""
     t = torch.tensor(vals, dtype=torch.float64, device=device)
@@ -1223,7 +1295,20 @@ def main():
     ap.add_argument("--no-exact", action="store_true")
     ap.add_argument("--no-flat", action="store_true")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the metric: validation against the generator, the copy ceiling, "
+                         "the e2e, config5, flat, exact-ends, file-CRC, seek, encode, codec, "
+                         "CPU-baseline and side-config fields (each with its --no-* switch); "
+                         "without it those fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one decoded as DIR/<name>.npy "
+                         "(dump_outputs; rank 0's shard)")
     args = ap.parse_args()
+    if not args.full:   # the plain run: set up, warm up, time the steps, print the result line
+        for leg in ("side_configs", "cpu_baseline", "validate", "e2e", "file_crc", "snappy", "lz4",
+                    "seek", "encode", "exact", "flat"):
+            setattr(args, "no_" + leg, True)
+        args.config5_gib = 0.0
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -1265,6 +1350,10 @@ def main():
                           int(gen[3][int(n_ent[:part].sum())]))
     achieved = alg / (ev_ms_max * 1e-3) / 1e9
 
+    if args.dump_outputs and rank == 0:   # before anything else touches the decoded columns
+        names = dump_outputs(args.dump_outputs, cols, ext_run, dev)
+        log(rank, f"outputs of the last timed step: {', '.join(names)} in {args.dump_outputs}")
+
     if not args.no_validate:
         validate(cols, ext, n_ent, gen, dev)
         if full > 1 or part:
@@ -1274,10 +1363,11 @@ def main():
 
 
     ceiling = None
-    try:   # the copy overwrites the decoded columns (validated above)
-        ceiling = copy_ceiling(batch, cols, alg, dev)   # rank 0's box is reported
-    except Exception as ex:  # reported, never the metric
-        log(rank, f"copy ceiling measurement failed: {ex}")
+    if args.full:
+        try:   # the copy overwrites the decoded columns (validated above)
+            ceiling = copy_ceiling(batch, cols, alg, dev)   # rank 0's box is reported
+        except Exception as ex:  # reported, never the metric
+            log(rank, f"copy ceiling measurement failed: {ex}")
 
     # The e2e leg runs before config5 and the flat leg: freeing their tens of GB of device memory
     # (torch.cuda.empty_cache) slows tpz_decode_blocks_host for the next ~1.5 s, 0.1037 -> 0.133 s
@@ -1321,9 +1411,11 @@ def main():
         except Exception as ex:  # reported, never the metric
             log(rank, f"config5 measurement failed: {ex}")
         cols = SlottedColumns(nb_run, batch.src_bytes, local)
-    decode_batch(ctx, batch, cols, stream)   # the decoded columns again (the seek field reads them)
+    if args.full:
+        decode_batch(ctx, batch, cols, stream)   # the decoded columns again (the seek field reads them)
 
-    side = rank == 0 and world == 1   # side measurements: single-GPU runs only (not the metric)
+    # side measurements: single-GPU --full runs only (not the metric)
+    side = args.full and rank == 0 and world == 1
     flat = None
     if side and not args.no_flat and full == 1 and part == 0:
         try:
@@ -1415,6 +1507,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,      # False: the fields that take runs of their own are null
             "settle_s": SETTLE_S,   # untimed decode steps before the warm-up (time_decode)
             "ms_per_step": round(wall_max * 1e3 / args.steps, 4),
             "higher_is_better": True,

@@ -3,7 +3,7 @@
 set -o pipefail
 OUT=${1:-gpurun_out/pmc}; shift
 mkdir -p "$OUT"; export TMPDIR=/tmp
-B="bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-validate $*"
+B="bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-validate $*"
 i=0
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_WAVES" \
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS" \
