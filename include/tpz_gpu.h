@@ -21,6 +21,8 @@
  *   tpz_format_block_error  the reference's error strings (checksum.rs:18-21, compress.rs:97,102)
  *   tpz_plan_blocks +       the write side for compaction output: SsTableBuilder::add +
  *   tpz_encode_blocks       block_build (src/table/builder.rs:49-85) over entries in HBM
+ *   tpz_merge_runs          MergeIterator over one SsTableIterator per input table, as sub_compact
+ *                           drives it (src/iterators/merge_iterator.rs:41-106, src/level.rs:178-222)
  *
  * Plain pointers and sizes only. Pointers named d_* are device (HBM) pointers of the context's
  * device; h_* are host pointers. `stream` is a hipStream_t passed as void* (NULL = default).
@@ -57,8 +59,13 @@ extern "C" {
  *      chunk overflow is TPZ_ERR_INTERNAL), and tpz_decode_check also fails for a wave path row
  *      claim that timed out or was overwritten; new entry point tpz_verify_files_flat_layout
  *      (open + flat layout from one read of the blocks)
+ *   7  compaction's merge step: tpz_merge_runs (MergeIterator over sorted runs in HBM) and
+ *      tpz_flat_entry_pos (flat columns -> tpz_entries), TPZ_MERGE_MAX_RUNS; no existing struct
+ *      or status changed. The bump also covers the three round-6 changes that version 6 took in
+ *      without one: the export tpz_verify_files_flat_layout, tpz_decode_check failing for a wave
+ *      path row claim, and TPZ_ERR_NOMEM of the host pipeline meaning a short caller buffer only
  * A consumer compiled against one header checks tpz_abi_version() == TPZ_ABI_VERSION. */
-#define TPZ_ABI_VERSION 6
+#define TPZ_ABI_VERSION 7
 int tpz_abi_version(void);
 
 /* ---- API return codes ------------------------------------------------------------------- */
@@ -614,6 +621,57 @@ tpz_err tpz_plan_blocks_async(tpz_ctx* ctx, const tpz_entries* entries, uint32_t
 tpz_err tpz_encode_blocks_async(tpz_ctx* ctx, const tpz_entries* entries, const uint32_t* d_first,
                                 const uint64_t* d_ext, const uint32_t* d_info, uint8_t* d_out,
                                 void* stream);
+
+/* ---- compaction's merge step, on the device ----------------------------------------------
+ * The step between the read side (tpz_decode_blocks_flat) and the write side (tpz_plan_blocks):
+ * sub_compact's MergeIterator over one SsTableIterator per input table (src/level.rs:178-222,
+ * src/iterators/merge_iterator.rs:41-106), with the entries staying in HBM.
+ *
+ * tpz_merge_runs: MergeIterator over n_runs sorted runs (merge_iterator.rs:41-106, as sub_compact
+ * drives it, level.rs:188-212). `entries` holds every run's entries back to back; run r is entries
+ * [h_run_first[r], h_run_first[r+1]) (h_run_first: n_runs + 1 non-decreasing u32 in HOST memory,
+ * h_run_first[0] = 0, h_run_first[n_runs] = entries->n_entries; a run may be empty: create()
+ * filters those out before it numbers the rest, :48-53). Every run is sorted non-decreasing by
+ * key (Rust's [u8] Ord: bytewise, unsigned, a proper prefix is smaller). The iterator then yields
+ *   - input entry (run r, position j) iff no run with a lower index holds an equal key (every copy
+ *     of a key repeated inside the winning run is yielded, every copy in the other runs is not);
+ *   - in the order (key, r, j).
+ * Empty values (tombstones) are entries like any other: sub_compact adds them to the builder.
+ *   d_out_keys, d_out_vals : the yielded keys / values, packed; 16-byte aligned, capacity
+ *                            entries->key_bytes / entries->val_bytes
+ *   d_out_kpos, d_out_vpos : capacity n_entries + 1 u64, valid up to index n_out: with the two
+ *                            byte columns a tpz_entries for tpz_plan_blocks_async
+ *   d_src_entry            : NULL, or capacity n_entries u32: d_src_entry[o] = the input entry
+ *                            output entry o is
+ *   d_info                 : 4 u64 of device memory: [0] = n_out, [1] = output key bytes,
+ *                            [2] = output value bytes, [3] = the first input entry with an empty
+ *                            key or UINT64_MAX (SsTableIterator::is_valid is false there and
+ *                            BlockBuilder::add asserts, builder.rs:27); when one is reported, the
+ *                            other outputs are unspecified (and stay within their capacities)
+ * Asynchronous on `stream`; uses the stream's grow-only workspace (about 40 bytes per entry).
+ * n_runs == 0 or n_entries == 0 gives n_out = 0. TPZ_ERR_INVALID_ARG for n_runs >
+ * TPZ_MERGE_MAX_RUNS, an h_run_first that breaks the rules above, or a misaligned output. Runs
+ * that are not sorted are a precondition violation: the outputs are then unspecified, but every
+ * loop is bounded, every index clamped, and nothing is written outside the stated capacities. */
+#define TPZ_MERGE_MAX_RUNS 256u
+tpz_err tpz_merge_runs(tpz_ctx* ctx, const tpz_entries* entries, const uint32_t* h_run_first,
+                       uint32_t n_runs, uint8_t* d_out_keys, uint64_t* d_out_kpos,
+                       uint8_t* d_out_vals, uint64_t* d_out_vpos, uint32_t* d_src_entry,
+                       uint64_t* d_info, void* stream);
+
+/* Flat columns -> the write side's entry positions: for the batch tpz_decode_blocks_flat decoded
+ * into `cols`, d_kpos[e] / d_vpos[e] (e <= n = d_first[n_blocks]; n + 1 u64 each) = the absolute
+ * start of entry e's key in cols->d_keys / value in cols->d_values, so that {d_keys, d_kpos,
+ * d_values, d_vpos, n} is a tpz_entries in SsTableIterator order. Block i, entry j < count[i]
+ * (e = d_first[i] + j): kpos = d_first[st + i] + (j ? ends[2(e-1)] : 0), vpos likewise;
+ * kpos[n] / vpos[n] = the column totals. A TPZ_BLOCK_BAD_ENTRY block reads as decoded (an
+ * unreadable key or value is empty). A block that decoded nothing (count[i] == 0 with its header's
+ * n slots reserved) gives its first slot the block's reserved byte range and leaves the others
+ * empty. d_info[0] (one u32) = the first block whose status is not TPZ_BLOCK_OK, or 0xFFFFFFFF:
+ * sub_compact's `?` fails the compaction at such a block (and the reference panics at a
+ * BAD_ENTRY block's bad entry), so the caller checks it. Asynchronous on `stream`. */
+tpz_err tpz_flat_entry_pos(tpz_ctx* ctx, const tpz_flat_columns* cols, uint32_t n_blocks,
+                           uint64_t* d_kpos, uint64_t* d_vpos, uint32_t* d_info, void* stream);
 
 /* ---- host write side (inputs for benches and the table facade) ---------------------------
  * SsTableBuilder::add + block_build (src/table/builder.rs:49-85) with BlockBuilder's fill rule

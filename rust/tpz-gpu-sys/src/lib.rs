@@ -36,10 +36,11 @@ pub const TPZ_ENTRY_OK: u8 = 0;
 pub const TPZ_ENTRY_BAD_VALUE: u8 = 1;
 pub const TPZ_ENTRY_BAD_KEY: u8 = 2;
 
-pub const TPZ_ABI_VERSION: c_int = 6;
+pub const TPZ_ABI_VERSION: c_int = 7;
 pub const TPZ_LDS_BLOCK_BYTES: u32 = 94192;
 pub const TPZ_BIGWAVE_BLOCK_BYTES: u32 = 0x40000000;
 pub const TPZ_PLAN_ASYNC_MAX_BLOCK: u32 = 10242;
+pub const TPZ_MERGE_MAX_RUNS: u32 = 256;
 
 /// `tpz_batch`: blocks (or ranges, or files) back to back in HBM; block i is
 /// `d_src[d_ext[i] .. d_ext[i + 1])`.
@@ -216,6 +217,13 @@ extern "C" {
     pub fn tpz_encode_blocks_async(ctx: *mut TpzCtx, entries: *const TpzEntries,
                                    d_first: *const u32, d_ext: *const u64, d_info: *const u32,
                                    d_out: *mut u8, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_merge_runs(ctx: *mut TpzCtx, entries: *const TpzEntries, h_run_first: *const u32,
+                          n_runs: u32, d_out_keys: *mut u8, d_out_kpos: *mut u64,
+                          d_out_vals: *mut u8, d_out_vpos: *mut u64, d_src_entry: *mut u32,
+                          d_info: *mut u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_flat_entry_pos(ctx: *mut TpzCtx, cols: *const TpzFlatColumns, n_blocks: u32,
+                              d_kpos: *mut u64, d_vpos: *mut u64, d_info: *mut u32,
+                              stream: *mut c_void) -> TpzErr;
     pub fn tpz_build_blocks(h_keys: *const u8, h_kpos: *const u64, h_vals: *const u8,
                             h_vpos: *const u64, n_entries: u64, block_size: u32, h_out: *mut u8,
                             out_cap: u64, h_ext: *mut u64, ext_cap: u64, n_blocks: *mut u64,

@@ -23,7 +23,9 @@ SUCCESS, ERR_INVALID_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_INTERNAL, ERR_S
  BLOCK_MALFORMED, BLOCK_OK_SPILLED, BLOCK_SPILL_FULL, BLOCK_CODEC_ERROR, BLOCK_BAD_ENTRY) = range(10)
 # tpz_entry_class (BAD_ENTRY blocks)
 ENTRY_OK, ENTRY_BAD_VALUE, ENTRY_BAD_KEY = 0, 1, 2
-ABI_VERSION = 6           # TPZ_ABI_VERSION this binding was written against
+ABI_VERSION = 7           # TPZ_ABI_VERSION this binding was written against
+MERGE_MAX_RUNS = 256      # TPZ_MERGE_MAX_RUNS
+MERGE_TILE = 1024         # entries per tile-merge workgroup of tpz_merge_runs (csrc kMergeTile)
 LDS_BLOCK_BYTES = 94192   # TPZ_LDS_BLOCK_BYTES: longer blocks with 64+ entries take the spill path
 BIGWAVE_BLOCK_BYTES = 0x40000000   # TPZ_BIGWAVE_BLOCK_BYTES
 
@@ -185,6 +187,12 @@ def lib() -> C.CDLL:
         L.tpz_encode_blocks_async.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tpz_encode_blocks_async.restype = C.c_int
+        L.tpz_merge_runs.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_void_p, C.c_uint32] + \
+            [C.c_void_p] * 7
+        L.tpz_merge_runs.restype = C.c_int
+        L.tpz_flat_entry_pos.argtypes = [C.c_void_p, C.POINTER(FlatColumns), C.c_uint32] + \
+            [C.c_void_p] * 4
+        L.tpz_flat_entry_pos.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -474,6 +482,25 @@ class Context:
         check(lib().tpz_encode_blocks_async(self.handle, C.byref(ent), C.c_void_p(d_first),
                                             C.c_void_p(d_ext), C.c_void_p(d_info), C.c_void_p(d_out),
                                             C.c_void_p(stream)), "tpz_encode_blocks_async")
+
+    def merge_runs_ptrs(self, ent: Entries, h_run_first: int, n_runs: int, d_out_keys: int,
+                        d_out_kpos: int, d_out_vals: int, d_out_vpos: int, d_src_entry: int,
+                        d_info: int, stream: int = 0) -> None:
+        """tpz_merge_runs: MergeIterator over n_runs sorted runs of `ent` (merge_iterator.rs:41-106);
+        h_run_first is a host pointer to n_runs + 1 u32."""
+        check(lib().tpz_merge_runs(self.handle, C.byref(ent), C.c_void_p(h_run_first), n_runs,
+                                   C.c_void_p(d_out_keys), C.c_void_p(d_out_kpos),
+                                   C.c_void_p(d_out_vals), C.c_void_p(d_out_vpos),
+                                   C.c_void_p(d_src_entry), C.c_void_p(d_info),
+                                   C.c_void_p(stream)), "tpz_merge_runs")
+
+    def flat_entry_pos_ptrs(self, cols: dict, n_blocks: int, d_kpos: int, d_vpos: int,
+                            d_info: int, stream: int = 0) -> None:
+        """tpz_flat_entry_pos: the flat columns' entry positions (cols maps FLAT_FIELDS -> pointer)."""
+        c = FlatColumns(*[cols[f] for f in FLAT_FIELDS])
+        check(lib().tpz_flat_entry_pos(self.handle, C.byref(c), n_blocks, C.c_void_p(d_kpos),
+                                       C.c_void_p(d_vpos), C.c_void_p(d_info), C.c_void_p(stream)),
+              "tpz_flat_entry_pos")
 
     def encode_blocks_ptrs(self, ent: Entries, d_first: int, d_ext: int, n_blocks: int,
                            d_out: int, stream: int = 0) -> None:

@@ -139,6 +139,8 @@ struct tpz_workspace {
   size_t bloom_cap = 0;
   void* d_comp = nullptr;       // tpz_compress_blocks: the per-block scratch slots + scan parts
   size_t comp_cap = 0;
+  void* d_merge = nullptr;      // tpz_merge_runs: prefixes, id lists, tile partitions, scan arrays
+  size_t merge_cap = 0;
   uint32_t* h_info = nullptr;   // pinned: tpz_plan_blocks' read-back of its 16-byte info
 };
 
@@ -165,6 +167,7 @@ void free_workspace(tpz_workspace& w) {
   if (w.d_plan1) (void)hipFree(w.d_plan1);
   if (w.d_bloom) (void)hipFree(w.d_bloom);
   if (w.d_comp) (void)hipFree(w.d_comp);
+  if (w.d_merge) (void)hipFree(w.d_merge);
   if (w.h_info) (void)hipHostFree(w.h_info);
   w = tpz_workspace{};
 }
@@ -960,6 +963,76 @@ tpz_err tpz_encode_blocks_async(tpz_ctx* c, const tpz_entries* en, const uint32_
   if (en->n_entries == 0) return TPZ_SUCCESS;
   // at most one block per entry: the worklist bound
   return encode_launch(c, en, d_first, d_ext, en->n_entries, d_info, d_out, stream);
+}
+
+tpz_err tpz_merge_runs(tpz_ctx* c, const tpz_entries* en, const uint32_t* h_run_first,
+                       uint32_t n_runs, uint8_t* d_out_keys, uint64_t* d_out_kpos,
+                       uint8_t* d_out_vals, uint64_t* d_out_vpos, uint32_t* d_src_entry,
+                       uint64_t* d_info, void* stream) {
+  if (!c || !en || !d_info || !d_out_kpos || !d_out_vpos) return TPZ_ERR_INVALID_ARG;
+  if (n_runs > TPZ_MERGE_MAX_RUNS || en->n_entries == 0xFFFFFFFFu) return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 15u) return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_out_kpos | (uintptr_t)d_out_vpos | (uintptr_t)d_info) & 7u) ||
+      ((uintptr_t)d_src_entry & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  const uint32_t n = n_runs ? en->n_entries : 0;   // no runs: nothing to yield
+  if (n_runs) {
+    if (!h_run_first || h_run_first[0] != 0 || h_run_first[n_runs] != n) return TPZ_ERR_INVALID_ARG;
+    for (uint32_t r = 0; r < n_runs; r++)
+      if (h_run_first[r] > h_run_first[r + 1]) return TPZ_ERR_INVALID_ARG;
+  }
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
+    TPZ_HIP(hipMemsetAsync(d_info + 3, 0xFF, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_out_kpos, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_out_vpos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  if (!en->d_kpos || !en->d_vpos || (!en->d_keys && en->key_bytes) || (!en->d_vals && en->val_bytes) ||
+      (!d_out_keys && en->key_bytes) || (!d_out_vals && en->val_bytes))
+    return TPZ_ERR_INVALID_ARG;
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_merge, &w.merge_cap, tpz::merge_work_bytes(n, n_runs));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_merge;
+  }
+  tpz::MergeLaunch a{};
+  a.keys = en->d_keys;
+  a.kpos = en->d_kpos;
+  a.key_bytes = en->key_bytes;
+  a.vals = en->d_vals;
+  a.vpos = en->d_vpos;
+  a.val_bytes = en->val_bytes;
+  a.n = n;
+  a.n_runs = n_runs;
+  a.run_first = h_run_first;
+  a.out_keys = d_out_keys;
+  a.out_kpos = d_out_kpos;
+  a.out_vals = d_out_vals;
+  a.out_vpos = d_out_vpos;
+  a.src_entry = d_src_entry;
+  a.info = d_info;
+  a.work = work;
+  TPZ_HIP(tpz::launch_merge(a, s));
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_flat_entry_pos(tpz_ctx* c, const tpz_flat_columns* cols, uint32_t n_blocks,
+                           uint64_t* d_kpos, uint64_t* d_vpos, uint32_t* d_info, void* stream) {
+  if (!c || !cols || !d_kpos || !d_vpos || !d_info) return TPZ_ERR_INVALID_ARG;
+  if (n_blocks && (!cols->d_first || !cols->d_ends || !cols->d_count || !cols->d_status))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::EntryPosLaunch a{cols->d_first, cols->d_ends, cols->d_count, cols->d_status, n_blocks,
+                        d_kpos, d_vpos, d_info};
+  tpz::launch_flat_entry_pos(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
 }
 
 tpz_err tpz_pack_ends(tpz_ctx* c, const tpz_batch* b, const tpz_columns* cols,

@@ -199,6 +199,44 @@ __global__ __launch_bounds__(256) void flat_scan_write(u64* first, u32 nb, const
   if (blockIdx.x == 0 && threadIdx.x == 0) a[nb] = pa[np];
 }
 
+// ------------------------------------------------------------------ flat columns -> tpz_entries
+// tpz_flat_entry_pos: one wave per block turns the block's {kend, vend} pairs (relative to its
+// first key / value byte) into absolute entry starts in the columns. A block that decoded nothing
+// keeps its n reserved slots: the first one spans the block's reserved bytes, the others are
+// empty, so the positions stay non-decreasing and end at the column totals.
+__global__ __launch_bounds__(256) void flat_entry_pos_kernel(const u64* first, const u32* ends,
+                                                              const u32* count, const uint8_t* status,
+                                                              u32 nb, u64* kpos, u64* vpos, u32* info) {
+  const u32 lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const u32 b = blockIdx.x * kFlWaves + wid;
+  if (b >= nb) return;
+  const u64 st = (u64)nb + 1;
+  const u64 e0 = first[b], e1 = first[b + 1];
+  const u64 kb = first[st + b], kn = first[st + b + 1];
+  const u64 vb = first[2 * st + b], vn = first[2 * st + b + 1];
+  const u32 stt = status[b];
+  if (stt != TPZ_BLOCK_OK && lane == 0) atomicMin(info, b);
+  u64 cnt = block_decoded(stt) ? count[b] : 0;
+  if (cnt > e1 - e0) cnt = e1 - e0;
+  for (u64 j = lane; j < e1 - e0; j += 64) {
+    const u64 e = e0 + j;
+    u64 k = kn, v = vn;              // (slots past the first of a block that decoded nothing)
+    if (j == 0) {
+      k = kb;
+      v = vb;
+    } else if (j < cnt) {
+      k = kb + ends[2 * (e - 1)];
+      v = vb + ends[2 * (e - 1) + 1];
+    }
+    kpos[e] = k;
+    vpos[e] = v;
+  }
+  if (b == nb - 1 && lane == 0) {
+    kpos[e1] = kn;
+    vpos[e1] = vn;
+  }
+}
+
 // ------------------------------------------------------------------ open -> flat layout, one read
 // tpz_verify_files_flat_layout: FileObject::open's whole-file CRC (src/table/file_object.rs:57-78)
 // of every SST file and tpz_flat_layout's per-block reservations of its data blocks from ONE read
@@ -510,6 +548,13 @@ void launch_scan_u64(u64* a, u32 n, u64* part, hipStream_t stream) {
   hipLaunchKernelGGL(flat_scan_write, dim3(np, 1), dim3(256), 0, stream, a, n, part, np);
 }
 
+void launch_scan3_u64(u64* a, u32 n, u64* part, hipStream_t stream) {
+  const u32 np = (n + kScWg - 1) / kScWg;
+  hipLaunchKernelGGL(flat_scan_parts, dim3(np, 3), dim3(256), 0, stream, a, n, part, np);
+  hipLaunchKernelGGL(flat_scan_totals, dim3(3), dim3(1024), 0, stream, part, np);
+  hipLaunchKernelGGL(flat_scan_write, dim3(np, 3), dim3(256), 0, stream, a, n, part, np);
+}
+
 void launch_flat_layout(const uint8_t* src, const u64* ext, u64 src_bytes, u32 n_blocks,
                         u64* first, u64* part, u32 num_cus, hipStream_t stream) {
   if (n_blocks == 0) {
@@ -518,10 +563,18 @@ void launch_flat_layout(const uint8_t* src, const u64* ext, u64 src_bytes, u32 n
   }
   hipLaunchKernelGGL(flat_sizes_kernel, dim3((n_blocks + kFlWaves - 1) / kFlWaves), dim3(256), 0,
                      stream, src, ext, src_bytes, n_blocks, first);
-  const u32 np = (n_blocks + kScWg - 1) / kScWg;
-  hipLaunchKernelGGL(flat_scan_parts, dim3(np, 3), dim3(256), 0, stream, first, n_blocks, part, np);
-  hipLaunchKernelGGL(flat_scan_totals, dim3(3), dim3(1024), 0, stream, part, np);
-  hipLaunchKernelGGL(flat_scan_write, dim3(np, 3), dim3(256), 0, stream, first, n_blocks, part, np);
+  launch_scan3_u64(first, n_blocks, part, stream);
+}
+
+void launch_flat_entry_pos(const EntryPosLaunch& a, hipStream_t stream) {
+  (void)hipMemsetAsync(a.info, 0xFF, 4, stream);
+  if (a.n_blocks == 0) {
+    (void)hipMemsetAsync(a.kpos, 0, 8, stream);
+    (void)hipMemsetAsync(a.vpos, 0, 8, stream);
+    return;
+  }
+  hipLaunchKernelGGL(flat_entry_pos_kernel, dim3((a.n_blocks + kFlWaves - 1) / kFlWaves), dim3(256),
+                     0, stream, a.first, a.ends, a.count, a.status, a.n_blocks, a.kpos, a.vpos, a.info);
 }
 
 static u32 op_pow_shift(u64 nbytes) {   // x^(8 n) mod P, reflected (x^0 = 0x80000000)

@@ -297,6 +297,45 @@ uint64_t flat_scan_parts_words(uint32_t n_blocks);
 // In place: a[i] = sum of a[j < i], a[n] = the total (n + 1 u64; part = flat_scan_parts_words(n)
 // / 3 u64 suffices).
 void launch_scan_u64(uint64_t* a, uint32_t n, uint64_t* part, hipStream_t stream);
+// Three arrays of n + 1 u64 back to back (a, a + n + 1, a + 2 (n + 1)), each scanned in place as
+// launch_scan_u64 does (the flat layout's scan); part = flat_scan_parts_words(n) u64. n > 0.
+void launch_scan3_u64(uint64_t* a, uint32_t n, uint64_t* part, hipStream_t stream);
+// tpz_flat_entry_pos (tpz_flat.hip): the flat columns' entry positions as a tpz_entries.
+struct EntryPosLaunch {
+  const uint64_t* first;   // tpz_flat_layout's 3 x (n_blocks + 1)
+  const uint32_t* ends;
+  const uint32_t* count;
+  const uint8_t* status;
+  uint32_t n_blocks;
+  uint64_t* kpos;
+  uint64_t* vpos;
+  uint32_t* info;          // [0] = first block whose status is not OK (0xFFFFFFFF: none)
+};
+void launch_flat_entry_pos(const EntryPosLaunch& a, hipStream_t stream);
+
+// tpz_merge_runs (tpz_merge.hip): MergeIterator over sorted runs of entries in HBM.
+constexpr uint32_t kMergeTile = 1024;   // entries per tile-merge workgroup (256 threads x 4)
+struct MergeLaunch {
+  const uint8_t* keys;
+  const uint64_t* kpos;
+  uint64_t key_bytes;
+  const uint8_t* vals;
+  const uint64_t* vpos;
+  uint64_t val_bytes;
+  uint32_t n;                 // > 0
+  uint32_t n_runs;            // 1 .. TPZ_MERGE_MAX_RUNS
+  const uint32_t* run_first;  // host: n_runs + 1, checked by the caller
+  uint8_t* out_keys;
+  uint64_t* out_kpos;
+  uint8_t* out_vals;
+  uint64_t* out_vpos;
+  uint32_t* src_entry;        // or null
+  uint64_t* info;             // 4 u64
+  void* work;                 // merge_work_bytes(n, n_runs) of device scratch
+};
+uint64_t merge_work_bytes(uint32_t n, uint32_t n_runs);
+hipError_t launch_merge(const MergeLaunch& a, hipStream_t stream);
+
 // tpz_compress_blocks (tpz_compress.hip): scratch bytes for the per-block slots; the snappy
 // encode, the scan of the sizes into dst_ext and the packing into dst.
 uint64_t compress_scratch_bytes(uint64_t src_bytes, uint32_t n_blocks);
