@@ -26,7 +26,11 @@ ENTRY_OK, ENTRY_BAD_VALUE, ENTRY_BAD_KEY = 0, 1, 2
 ABI_VERSION = 7           # TPZ_ABI_VERSION this binding was written against
 MERGE_MAX_RUNS = 256      # TPZ_MERGE_MAX_RUNS
 MERGE_TILE = 1024         # entries per tile-merge workgroup of tpz_merge_runs (csrc kMergeTile)
-LDS_BLOCK_BYTES = 94192   # TPZ_LDS_BLOCK_BYTES: longer blocks with 64+ entries take the spill path
+MERGE_LANE_COPY_MAX = 256  # longer keys / values are copied by the whole wave (csrc kLaneCopyMax)
+BLOOM_SLICE_BITS = 1 << 19  # bits per slice of tpz_bloom_build's partitioned path (csrc kBloomSliceBits)
+BLOOM_MAX_SLICES = 1024   # filters of more slices take the atomic kernel (csrc kBloomMaxSlices)
+BLOOM_WG_PROBES = 12288   # a workgroup takes BLOOM_WG_PROBES // k keys (csrc kBloomWgProbes)
+LDS_BLOCK_BYTES = 94192  # TPZ_LDS_BLOCK_BYTES: longer blocks with 64+ entries take the spill path
 BIGWAVE_BLOCK_BYTES = 0x40000000   # TPZ_BIGWAVE_BLOCK_BYTES
 
 

@@ -479,13 +479,12 @@ class Bloom:
         self.filter = bytes(filt)
 
     @staticmethod
-    def from_keys(hashes, fpp: float) -> "Bloom":
-        """Bloom::from_keys (bloom.rs:48-70): m = -n ln(fpp) / ln2^2 bits, k = ceil(m / n ln2^2)
-        probes clamped to [1, 15] (stored in the last byte), probe i of hash h at
-        (h + i * rotr(h, 34)) mod limit."""
+    def geometry(n_keys: int, fpp: float) -> tuple[int, int]:
+        """The sizing of Bloom::from_keys (bloom.rs:48-57) for n_keys hashes: (filter length in
+        bytes, the k byte included; k)."""
         if not (0.0 <= fpp < 1.0):
             raise ReferencePanic("assertion failed: (0.0..1.0).contains(&fpp)")
-        n = float(len(hashes))
+        n = float(n_keys)
         ln2sq = math.log(2.0) * math.log(2.0)           # LN_2.powi(2)
         lnf = math.log(fpp) if fpp > 0.0 else -math.inf
         num = n * lnf
@@ -495,7 +494,15 @@ class Bloom:
         k = (m / n * ln2sq) if n > 0 else math.nan
         k = max(1, min(15, _sat_cast(math.ceil(k) if k == k and abs(k) != math.inf else k, 255)))
         nbits = _sat_cast(math.ceil(m) if m == m and abs(m) != math.inf else m, 1 << 64)
-        filt = bytearray((nbits + 7) // 8 + 1)
+        return (nbits + 7) // 8 + 1, k
+
+    @staticmethod
+    def from_keys(hashes, fpp: float) -> "Bloom":
+        """Bloom::from_keys (bloom.rs:48-70): m = -n ln(fpp) / ln2^2 bits, k = ceil(m / n ln2^2)
+        probes clamped to [1, 15] (stored in the last byte), probe i of hash h at
+        (h + i * rotr(h, 34)) mod limit."""
+        nbytes, k = Bloom.geometry(len(hashes), fpp)
+        filt = bytearray(nbytes)
         filt[-1] = k
         limit = (len(filt) - 1) * 8
         mask = (1 << 64) - 1
