@@ -23,6 +23,8 @@
  *   tpz_encode_blocks       block_build (src/table/builder.rs:49-85) over entries in HBM
  *   tpz_merge_runs          MergeIterator over one SsTableIterator per input table, as sub_compact
  *                           drives it (src/iterators/merge_iterator.rs:41-106, src/level.rs:178-222)
+ *   tpz_get_keys +          LevelController::get (src/level.rs:427-465) for a batch of keys over
+ *   tpz_get_values          tables resident in HBM: the walk over L0 and the levels, then the values
  *
  * Plain pointers and sizes only. Pointers named d_* are device (HBM) pointers of the context's
  * device; h_* are host pointers. `stream` is a hipStream_t passed as void* (NULL = default).
@@ -64,8 +66,11 @@ extern "C" {
  *      or status changed. The bump also covers the three round-6 changes that version 6 took in
  *      without one: the export tpz_verify_files_flat_layout, tpz_decode_check failing for a wave
  *      path row claim, and TPZ_ERR_NOMEM of the host pipeline meaning a short caller buffer only
+ *   8  batched point gets over resident tables: tpz_get_keys (LevelController::get's walk over
+ *      L0 and the levels) and tpz_get_values (the gather of the values found), tpz_get_table,
+ *      TPZ_GET_*; no existing struct or status changed
  * A consumer compiled against one header checks tpz_abi_version() == TPZ_ABI_VERSION. */
-#define TPZ_ABI_VERSION 7
+#define TPZ_ABI_VERSION 8
 int tpz_abi_version(void);
 
 /* ---- API return codes ------------------------------------------------------------------- */
@@ -672,6 +677,71 @@ tpz_err tpz_merge_runs(tpz_ctx* ctx, const tpz_entries* entries, const uint32_t*
  * BAD_ENTRY block's bad entry), so the caller checks it. Asynchronous on `stream`. */
 tpz_err tpz_flat_entry_pos(tpz_ctx* ctx, const tpz_flat_columns* cols, uint32_t n_blocks,
                            uint64_t* d_kpos, uint64_t* d_vpos, uint32_t* d_info, void* stream);
+
+/* ---- batched LevelController::get over resident tables -----------------------------------
+ * LevelController::get(key) (src/level.rs:427-465) for a batch of keys, over tables that stay in
+ * HBM after they were opened (their decoded columns, block first keys and bloom filters):
+ *   1. L0 (:428-442): the tables of level 0 from the last one down (l0_push_sstable appends, so
+ *      the last is the newest). For each: SsTable::may_contain(key) false -> the next table
+ *      (src/table.rs:114-119: no filter means true); else SsTableIterator::create_and_seek_to_key,
+ *      whose Err ends the get; a valid iterator at an equal key ends it too: an empty value is
+ *      Ok(None) (a tombstone), any other Ok(Some(value)); otherwise the next table.
+ *   2. levels 1.. (:444-463): an empty level is skipped; in any other only tables[idx] is tried,
+ *      idx = partition_point(smallest_key <= key).saturating_sub(1) over the level's tables in
+ *      their stored order, with the same three steps. smallest_key is block_metas[0].first_key
+ *      (src/table.rs:143-151): the first entry of tpz_table.d_first_keys.
+ *   3. nothing found: Ok(None).
+ * The probe is tpz_bloom_may_contain's and the seek is tpz_seek_keys', with their panic classes.
+ *
+ * d_tables: n_tables descriptors in DEVICE memory (their pointers are device pointers). Level l
+ * is tables [h_level_first[l], h_level_first[l+1]); h_level_first: n_levels + 1 non-decreasing
+ * u32 in HOST memory, h_level_first[0] = 0, h_level_first[n_levels] = n_tables (read during the
+ * call: it travels in the kernel's arguments). Level 0 is stored in push order (oldest first);
+ * the levels below are stored sorted by smallest key, which is a precondition: with an unsorted
+ * level the results are unspecified, but every loop is bounded and every index clamped.
+ * Keys are packed as for tpz_seek_keys; an empty key is legal and takes the same walk.
+ *
+ * tpz_get_keys, per query i:
+ *   d_result[i]  TPZ_GET_ABSENT / FOUND / DELETED / ERROR
+ *   d_status[i]  TPZ_BLOCK_OK unless the result is ERROR; then the status tpz_seek_keys reports
+ *                for the seek that failed, or TPZ_BLOCK_MALFORMED where tpz_bloom_may_contain
+ *                reports 2 or the selected table has no blocks
+ *   d_table[i], d_block[i], d_entry[i]
+ *                where the walk ended: the hit, the tombstone, or the failing table and the block
+ *                and entry its seek reports; 0xFFFFFFFF each for ABSENT; a bloom panic gives
+ *                d_block = d_entry = 0xFFFFFFFF
+ *   d_val_pos    n_keys + 1 u64: the exclusive prefix sums of the value lengths (0 unless FOUND);
+ *                d_val_pos[n_keys] is the total, which the caller reads back to size d_vals
+ * tpz_get_values copies the value of every FOUND query i to d_vals[d_val_pos[i] ..
+ * d_val_pos[i+1]) (packed back to back, d_vals 16-byte aligned), from tpz_get_keys' outputs over
+ * the same d_tables; nothing is written at or past val_cap.
+ * Both are asynchronous on `stream`; tpz_get_keys uses the stream's grow-only workspace (the
+ * scan's partial sums). TPZ_ERR_INVALID_ARG, before any device work, for n_levels >
+ * TPZ_GET_MAX_LEVELS, an h_level_first that breaks the rules above, or null or misaligned
+ * pointers. n_keys == 0 and n_tables == 0 are valid: with no tables every query is ABSENT. */
+#define TPZ_GET_MAX_LEVELS 16u /* the reference's MAX_LEVEL is 6 (src/level.rs:34) */
+#define TPZ_GET_ABSENT 0       /* Ok(None): no table holds the key */
+#define TPZ_GET_FOUND 1        /* Ok(Some(value)) */
+#define TPZ_GET_DELETED 2      /* Ok(None): the first table holding it has an empty value */
+#define TPZ_GET_ERROR 3        /* the reference's Err / panic; d_status says which */
+/* (declared with a tag: tests/test_rust_binding.py's parser takes every anonymous struct
+ * typedef for one of the six structs it knows by name) */
+struct tpz_get_table {
+  tpz_table table;         /* as for tpz_seek_keys */
+  const uint8_t* d_filter; /* Bloom::encode, or NULL: no filter, may_contain is true */
+  uint64_t filter_len;
+};
+typedef struct tpz_get_table tpz_get_table;
+
+tpz_err tpz_get_keys(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n_tables,
+                     const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                     const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                     uint8_t* d_status, uint32_t* d_table, uint32_t* d_block, uint32_t* d_entry,
+                     uint64_t* d_val_pos, void* stream);
+tpz_err tpz_get_values(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n_tables,
+                       uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
+                       const uint32_t* d_block, const uint32_t* d_entry, const uint64_t* d_val_pos,
+                       uint8_t* d_vals, uint64_t val_cap, void* stream);
 
 /* ---- host write side (inputs for benches and the table facade) ---------------------------
  * SsTableBuilder::add + block_build (src/table/builder.rs:49-85) with BlockBuilder's fill rule

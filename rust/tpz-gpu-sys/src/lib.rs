@@ -36,11 +36,18 @@ pub const TPZ_ENTRY_OK: u8 = 0;
 pub const TPZ_ENTRY_BAD_VALUE: u8 = 1;
 pub const TPZ_ENTRY_BAD_KEY: u8 = 2;
 
-pub const TPZ_ABI_VERSION: c_int = 7;
+pub const TPZ_ABI_VERSION: c_int = 8;
 pub const TPZ_LDS_BLOCK_BYTES: u32 = 94192;
 pub const TPZ_BIGWAVE_BLOCK_BYTES: u32 = 0x40000000;
 pub const TPZ_PLAN_ASYNC_MAX_BLOCK: u32 = 10242;
 pub const TPZ_MERGE_MAX_RUNS: u32 = 256;
+pub const TPZ_GET_MAX_LEVELS: u32 = 16;
+
+/// `tpz_get_keys`' `d_result`, one byte per query.
+pub const TPZ_GET_ABSENT: u8 = 0;
+pub const TPZ_GET_FOUND: u8 = 1;
+pub const TPZ_GET_DELETED: u8 = 2;
+pub const TPZ_GET_ERROR: u8 = 3;
 
 /// `tpz_batch`: blocks (or ranges, or files) back to back in HBM; block i is
 /// `d_src[d_ext[i] .. d_ext[i + 1])`.
@@ -123,6 +130,19 @@ pub struct TpzTable {
     pub d_spill_off: *const u64,
     pub d_entry_first: *const u64,
 }
+
+/// `tpz_get_table`: a resident table of `tpz_get_keys`: its `tpz_table` plus its bloom filter
+/// (`d_filter` null: the table has none and `may_contain` is true).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct TpzGetTable {
+    pub table: TpzTable,
+    pub d_filter: *const u8,
+    pub filter_len: u64,
+}
+/// The header declares this struct with a tag, so the extern block names it as the header does.
+#[allow(non_camel_case_types)]
+pub type tpz_get_table = TpzGetTable;
 
 /// `tpz_entries`: sorted entries in HBM (the write side).
 #[repr(C)]
@@ -221,6 +241,15 @@ extern "C" {
                           n_runs: u32, d_out_keys: *mut u8, d_out_kpos: *mut u64,
                           d_out_vals: *mut u8, d_out_vpos: *mut u64, d_src_entry: *mut u32,
                           d_info: *mut u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_get_keys(ctx: *mut TpzCtx, d_tables: *const tpz_get_table, n_tables: u32,
+                        h_level_first: *const u32, n_levels: u32, d_keys: *const u8,
+                        d_key_pos: *const u64, n_keys: u32, d_result: *mut u8, d_status: *mut u8,
+                        d_table: *mut u32, d_block: *mut u32, d_entry: *mut u32,
+                        d_val_pos: *mut u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_get_values(ctx: *mut TpzCtx, d_tables: *const tpz_get_table, n_tables: u32,
+                          n_keys: u32, d_result: *const u8, d_table: *const u32,
+                          d_block: *const u32, d_entry: *const u32, d_val_pos: *const u64,
+                          d_vals: *mut u8, val_cap: u64, stream: *mut c_void) -> TpzErr;
     pub fn tpz_flat_entry_pos(ctx: *mut TpzCtx, cols: *const TpzFlatColumns, n_blocks: u32,
                               d_kpos: *mut u64, d_vpos: *mut u64, d_info: *mut u32,
                               stream: *mut c_void) -> TpzErr;

@@ -23,7 +23,10 @@ SUCCESS, ERR_INVALID_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_INTERNAL, ERR_S
  BLOCK_MALFORMED, BLOCK_OK_SPILLED, BLOCK_SPILL_FULL, BLOCK_CODEC_ERROR, BLOCK_BAD_ENTRY) = range(10)
 # tpz_entry_class (BAD_ENTRY blocks)
 ENTRY_OK, ENTRY_BAD_VALUE, ENTRY_BAD_KEY = 0, 1, 2
-ABI_VERSION = 7           # TPZ_ABI_VERSION this binding was written against
+ABI_VERSION = 8           # TPZ_ABI_VERSION this binding was written against
+GET_MAX_LEVELS = 16       # TPZ_GET_MAX_LEVELS
+GET_ABSENT, GET_FOUND, GET_DELETED, GET_ERROR = range(4)   # tpz_get_keys' d_result (TPZ_GET_*)
+GET_NONE = 0xFFFFFFFF     # d_table / d_block / d_entry of a walk that ended nowhere
 MERGE_MAX_RUNS = 256      # TPZ_MERGE_MAX_RUNS
 MERGE_TILE = 1024         # entries per tile-merge workgroup of tpz_merge_runs (csrc kMergeTile)
 MERGE_LANE_COPY_MAX = 256  # longer keys / values are copied by the whole wave (csrc kLaneCopyMax)
@@ -70,6 +73,12 @@ class Table(C.Structure):
                 ("n_blocks", C.c_uint32), ("d_data", C.c_void_p), ("d_ends", C.c_void_p),
                 ("d_count", C.c_void_p), ("d_status", C.c_void_p), ("d_spill", C.c_void_p),
                 ("d_spill_off", C.c_void_p), ("d_entry_first", C.c_void_p)]
+
+
+class GetTable(C.Structure):
+    """tpz_get_table: a resident table of tpz_get_keys (its tpz_table plus its bloom filter;
+    d_filter None: no filter)."""
+    _fields_ = [("table", Table), ("d_filter", C.c_void_p), ("filter_len", C.c_uint64)]
 
 
 class Entries(C.Structure):
@@ -197,6 +206,12 @@ def lib() -> C.CDLL:
         L.tpz_flat_entry_pos.argtypes = [C.c_void_p, C.POINTER(FlatColumns), C.c_uint32] + \
             [C.c_void_p] * 4
         L.tpz_flat_entry_pos.restype = C.c_int
+        L.tpz_get_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
+        L.tpz_get_keys.restype = C.c_int
+        L.tpz_get_values.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + \
+            [C.c_void_p] * 6 + [C.c_uint64, C.c_void_p]
+        L.tpz_get_values.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -497,6 +512,29 @@ class Context:
                                    C.c_void_p(d_out_vals), C.c_void_p(d_out_vpos),
                                    C.c_void_p(d_src_entry), C.c_void_p(d_info),
                                    C.c_void_p(stream)), "tpz_merge_runs")
+
+    def get_keys_ptrs(self, d_tables: int, n_tables: int, h_level_first: int, n_levels: int,
+                      d_keys: int, d_key_pos: int, n_keys: int, d_result: int, d_status: int,
+                      d_table: int, d_block: int, d_entry: int, d_val_pos: int,
+                      stream: int = 0) -> None:
+        """tpz_get_keys: LevelController::get's walk for every key (level.rs:427-465) over the
+        n_tables tpz_get_table descriptors at d_tables; h_level_first is a host pointer to
+        n_levels + 1 u32."""
+        check(lib().tpz_get_keys(self.handle, C.c_void_p(d_tables), n_tables,
+                                 C.c_void_p(h_level_first), n_levels, C.c_void_p(d_keys),
+                                 C.c_void_p(d_key_pos), n_keys, C.c_void_p(d_result),
+                                 C.c_void_p(d_status), C.c_void_p(d_table), C.c_void_p(d_block),
+                                 C.c_void_p(d_entry), C.c_void_p(d_val_pos), C.c_void_p(stream)),
+              "tpz_get_keys")
+
+    def get_values_ptrs(self, d_tables: int, n_tables: int, n_keys: int, d_result: int,
+                        d_table: int, d_block: int, d_entry: int, d_val_pos: int, d_vals: int,
+                        val_cap: int, stream: int = 0) -> None:
+        """tpz_get_values: the values of tpz_get_keys' FOUND queries, packed at d_val_pos."""
+        check(lib().tpz_get_values(self.handle, C.c_void_p(d_tables), n_tables, n_keys,
+                                   C.c_void_p(d_result), C.c_void_p(d_table), C.c_void_p(d_block),
+                                   C.c_void_p(d_entry), C.c_void_p(d_val_pos), C.c_void_p(d_vals),
+                                   val_cap, C.c_void_p(stream)), "tpz_get_values")
 
     def flat_entry_pos_ptrs(self, cols: dict, n_blocks: int, d_kpos: int, d_vpos: int,
                             d_info: int, stream: int = 0) -> None:

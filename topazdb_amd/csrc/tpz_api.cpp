@@ -141,6 +141,8 @@ struct tpz_workspace {
   size_t comp_cap = 0;
   void* d_merge = nullptr;      // tpz_merge_runs: prefixes, id lists, tile partitions, scan arrays
   size_t merge_cap = 0;
+  void* d_get = nullptr;        // tpz_get_keys: the value-length scan's partial sums
+  size_t get_cap = 0;
   uint32_t* h_info = nullptr;   // pinned: tpz_plan_blocks' read-back of its 16-byte info
 };
 
@@ -168,6 +170,7 @@ void free_workspace(tpz_workspace& w) {
   if (w.d_bloom) (void)hipFree(w.d_bloom);
   if (w.d_comp) (void)hipFree(w.d_comp);
   if (w.d_merge) (void)hipFree(w.d_merge);
+  if (w.d_get) (void)hipFree(w.d_get);
   if (w.h_info) (void)hipHostFree(w.h_info);
   w = tpz_workspace{};
 }
@@ -1019,6 +1022,71 @@ tpz_err tpz_merge_runs(tpz_ctx* c, const tpz_entries* en, const uint32_t* h_run_
   a.info = d_info;
   a.work = work;
   TPZ_HIP(tpz::launch_merge(a, s));
+  return TPZ_SUCCESS;
+}
+
+// Level l of tpz_get_keys is tables [h[l], h[l+1]): n_levels + 1 non-decreasing u32 from 0 to
+// n_tables (no levels: no tables).
+static bool level_first_ok(const uint32_t* h, uint32_t n_levels, uint32_t n_tables) {
+  if (n_levels > TPZ_GET_MAX_LEVELS) return false;
+  if (n_levels == 0) return n_tables == 0;
+  if (!h || h[0] != 0 || h[n_levels] != n_tables) return false;
+  for (uint32_t l = 0; l < n_levels; l++)
+    if (h[l] > h[l + 1]) return false;
+  return true;
+}
+
+tpz_err tpz_get_keys(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
+                     const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                     const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                     uint8_t* d_status, uint32_t* d_table, uint32_t* d_block, uint32_t* d_entry,
+                     uint64_t* d_val_pos, void* stream) {
+  if (!c || !d_key_pos || !d_result || !d_status || !d_table || !d_block || !d_entry || !d_val_pos ||
+      (n_tables && !d_tables))
+    return TPZ_ERR_INVALID_ARG;
+  if (!level_first_ok(h_level_first, n_levels, n_tables) || n_keys == 0xFFFFFFFFu)
+    return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_tables | (uintptr_t)d_key_pos | (uintptr_t)d_val_pos) & 7u) ||
+      (((uintptr_t)d_table | (uintptr_t)d_block | (uintptr_t)d_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_keys == 0) {
+    TPZ_HIP(hipMemsetAsync(d_val_pos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* part = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_get, &w.get_cap, 8 * (tpz::flat_scan_parts_words(n_keys) / 3));
+    if (r != TPZ_SUCCESS) return r;
+    part = w.d_get;
+  }
+  tpz::GetLaunch a{d_tables, n_tables, h_level_first, n_levels, d_keys, d_key_pos, n_keys,
+                   d_result, d_status, d_table, d_block, d_entry, d_val_pos,
+                   static_cast<uint64_t*>(part)};
+  tpz::launch_get_walk(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_get_values(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
+                       uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
+                       const uint32_t* d_block, const uint32_t* d_entry, const uint64_t* d_val_pos,
+                       uint8_t* d_vals, uint64_t val_cap, void* stream) {
+  if (!c || (n_tables && !d_tables) || (val_cap && !d_vals) ||
+      (n_keys && (!d_result || !d_table || !d_block || !d_entry || !d_val_pos)))
+    return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_vals & 15u) || (((uintptr_t)d_tables | (uintptr_t)d_val_pos) & 7u) ||
+      (((uintptr_t)d_table | (uintptr_t)d_block | (uintptr_t)d_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  if (n_keys == 0 || val_cap == 0) return TPZ_SUCCESS;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::GetGatherLaunch a{d_tables, n_tables, n_keys, d_result, d_table, d_block, d_entry,
+                         d_val_pos, d_vals, val_cap};
+  tpz::launch_get_gather(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }
 

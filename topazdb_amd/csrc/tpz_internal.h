@@ -336,6 +336,38 @@ struct MergeLaunch {
 uint64_t merge_work_bytes(uint32_t n, uint32_t n_runs);
 hipError_t launch_merge(const MergeLaunch& a, hipStream_t stream);
 
+// tpz_get_keys / tpz_get_values (tpz_get.hip): LevelController::get over resident tables.
+struct GetLaunch {
+  const tpz_get_table* tabs;    // device
+  uint32_t n_tables;
+  const uint32_t* level_first;  // host: n_levels + 1, checked by the caller
+  uint32_t n_levels;            // <= TPZ_GET_MAX_LEVELS
+  const uint8_t* q;
+  const uint64_t* q_pos;
+  uint32_t n_q;                 // > 0
+  uint8_t* result;
+  uint8_t* status;
+  uint32_t* table;
+  uint32_t* block;
+  uint32_t* entry;
+  uint64_t* val_pos;            // n_q + 1: the value lengths, then scanned in place
+  uint64_t* part;               // flat_scan_parts_words(n_q) / 3 u64 of device scratch
+};
+void launch_get_walk(const GetLaunch& a, hipStream_t stream);
+struct GetGatherLaunch {
+  const tpz_get_table* tabs;
+  uint32_t n_tables;
+  uint32_t n_q;                 // > 0
+  const uint8_t* result;
+  const uint32_t* table;
+  const uint32_t* block;
+  const uint32_t* entry;
+  const uint64_t* val_pos;
+  uint8_t* vals;
+  uint64_t val_cap;
+};
+void launch_get_gather(const GetGatherLaunch& a, hipStream_t stream);
+
 // tpz_compress_blocks (tpz_compress.hip): scratch bytes for the per-block slots; the snappy
 // encode, the scan of the sizes into dst_ext and the packing into dst.
 uint64_t compress_scratch_bytes(uint64_t src_bytes, uint32_t n_blocks);

@@ -26,35 +26,17 @@
 
 #include "tpz_internal.h"
 #include "tpz_xxh3.h"
+#include "tpz_seek_dev.h"
 
 namespace tpz {
 
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-
-// memcmp then length, as Rust's Ord for [u8]
-__device__ __forceinline__ int key_cmp(const uint8_t* a, u64 al, const uint8_t* b, u64 bl) {
-  const u64 n = al < bl ? al : bl;
-  for (u64 i = 0; i < n; i++) {
-    const u32 x = a[i], y = b[i];
-    if (x != y) return x < y ? -1 : 1;
-  }
-  return al < bl ? -1 : (al > bl ? 1 : 0);
-}
+using seekdev::u32;
+using seekdev::u64;
 
 struct SeekParams {
-  const uint8_t* fk;        // block first keys, packed
-  const u64* fk_pos;        // n_blocks + 1
-  u32 n_blocks;
-  const u64* ext;           // the data region's block extents (slot bases)
-  const uint8_t* data;      // decoded columns
-  const u32* ends;
-  const u32* count;
-  const uint8_t* bstatus;
-  const uint8_t* spill;     // spill arena + record offsets (OK_SPILLED blocks)
-  const u64* spill_off;
+  tpz_table t;              // block first keys + the decoded columns (include/tpz_gpu.h)
   const uint8_t* q;         // query keys, packed
   const u64* q_pos;         // n_q + 1
   u32 n_q;
@@ -62,101 +44,17 @@ struct SeekParams {
   u32* out_entry;
   uint8_t* out_status;
   uint8_t* out_valid;
-  const u64* efirst;        // exact ends layout, or null: slotted
 };
-
-// A decoded block's ends and stream: its slot, or its spill record (include/tpz_gpu.h); the
-// entry classes of a BAD_ENTRY block (null otherwise: every entry reads whole).
-struct BlockView {
-  const u32* ends;
-  const uint8_t* stream;
-  const uint8_t* cls;
-  // seek_to(j) / the bisection's key read panic on entry j (iterator.rs:74-82, :95-98)
-  __device__ __forceinline__ bool seek_panics(u32 j) const { return cls && cls[j] != TPZ_ENTRY_OK; }
-  __device__ __forceinline__ bool key_panics(u32 j) const { return cls && cls[j] == TPZ_ENTRY_BAD_KEY; }
-};
-__device__ __forceinline__ BlockView block_view(const SeekParams& p, u32 b, u32 st) {
-  if (block_in_spill(st)) {
-    const u32 n = p.count[b];
-    const uint8_t* r = p.spill + p.spill_off[b];
-    const u32* e = reinterpret_cast<const u32*>(r);
-    const uint8_t* cls = (st == TPZ_BLOCK_BAD_ENTRY && n)
-                             ? r + spill_classes(n, e[2 * (n - 1)], e[2 * (n - 1) + 1]) : nullptr;
-    return BlockView{e, r + spill_stream(n), cls};
-  }
-  const u64 e0 = p.ext[b];
-  return BlockView{p.ends + 2 * ends_base(p.efirst, e0, b), p.data + slot_base(e0, b), nullptr};
-}
-// Entry j's key: its bytes and length.
-__device__ __forceinline__ const uint8_t* entry_key(const BlockView& v, u32 j, u64& len) {
-  const u32 lo = j ? v.ends[2 * (j - 1)] : 0u, hi = v.ends[2 * j];
-  len = hi - lo;
-  return v.stream + lo;
-}
-__device__ __forceinline__ bool decoded(u32 st) { return block_decoded(st); }
 
 __global__ __launch_bounds__(256) void seek_kernel(SeekParams p) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n_q) return;
-  const uint8_t* qk = p.q + p.q_pos[i];
-  const u64 ql = p.q_pos[i + 1] - p.q_pos[i];
-  if (p.n_blocks == 0) {                      // block_metas[0]: the reference panics
-    p.out_block[i] = 0;
-    p.out_entry[i] = 0;
-    p.out_status[i] = TPZ_BLOCK_MALFORMED;
-    p.out_valid[i] = 0;
-    return;
-  }
-  // find_block_idx: partition_point(first_key <= key) (the lower-bound bisection), minus one
-  u32 lo = 0, hi = p.n_blocks;
-  while (lo < hi) {
-    const u32 mid = lo + (hi - lo) / 2;
-    const u64 a = p.fk_pos[mid];
-    if (key_cmp(p.fk + a, p.fk_pos[mid + 1] - a, qk, ql) <= 0) lo = mid + 1; else hi = mid;
-  }
-  u32 b = lo ? lo - 1 : 0;
-  u32 st = p.bstatus[b], pos = 0;
-  bool valid = false, panic = false;
-  if (decoded(st)) {
-    // BlockIterator::seek_to_key
-    const BlockView v = block_view(p, b, st);
-    const u32 n = p.count[b];
-    u32 l = 0, r = n;
-    pos = n;
-    bool found = false;
-    while (l < r) {
-      const u32 mid = (r - l) / 2 + l;
-      if (v.key_panics(mid)) { pos = mid; panic = true; break; }   // iterator.rs:95-98
-      u64 kl;
-      const uint8_t* k = entry_key(v, mid, kl);
-      const int c = key_cmp(k, kl, qk, ql);
-      if (c > 0) r = mid;
-      else if (c < 0) l = mid + 1;
-      else { pos = mid; found = true; break; }
-    }
-    if (!found && !panic) pos = l;
-    if (!panic && pos < n && v.seek_panics(pos)) panic = true;      // seek_to, :74-82
-    u64 kl = 0;
-    if (pos < n) entry_key(v, pos, kl);
-    valid = !panic && pos < n && kl > 0;      // is_valid: the current key is non-empty
-    if (!panic && !valid && b + 1 < p.n_blocks) {   // the next block, from its first entry
-      b++;
-      st = p.bstatus[b];
-      pos = 0;
-      valid = false;
-      if (decoded(st) && p.count[b] > 0) {
-        const BlockView w = block_view(p, b, st);
-        panic = w.seek_panics(0);
-        entry_key(w, 0, kl);
-        valid = !panic && kl > 0;
-      }
-    }
-  }
-  p.out_block[i] = b;
-  p.out_entry[i] = pos;
-  p.out_status[i] = panic ? (uint8_t)TPZ_BLOCK_MALFORMED
-                          : decoded(st) ? (uint8_t)TPZ_BLOCK_OK : (uint8_t)st;
-  p.out_valid[i] = decoded(st) && valid;
+  const u64 a = p.q_pos[i];
+  const seekdev::SeekPos r = seekdev::seek_table(p.t, p.q + a, p.q_pos[i + 1] - a);
+  p.out_block[i] = r.block;
+  p.out_entry[i] = r.entry;
+  p.out_status[i] = (uint8_t)r.status;
+  p.out_valid[i] = r.valid;
 }
 
 struct BloomParams {
@@ -172,28 +70,8 @@ __global__ __launch_bounds__(256) void bloom_kernel(BloomParams p) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n_q) return;
   const u64 a = p.q_pos[i];
-  u64 h = xxh3::hash64(p.q + a, p.q_pos[i + 1] - a);
-  if (p.filter_len == 0) {                    // filter.last().unwrap() panics
-    p.out[i] = 2;
-    return;
-  }
-  const u64 delta = (h >> 34) | (h << 30);
-  const u32 k = p.filter[p.filter_len - 1];
-  const u64 limit = (p.filter_len - 1) * 8;
-  if (limit == 0) {                           // no bit array: `% 0` panics unless k == 0
-    p.out[i] = k ? 2 : 1;
-    return;
-  }
-  uint8_t hit = 1;
-  for (u32 j = 0; j < k; j++) {
-    const u64 bit = h % limit;
-    if (!(p.filter[bit >> 3] & (1u << (bit & 7)))) {
-      hit = 0;
-      break;
-    }
-    h += delta;
-  }
-  p.out[i] = hit;
+  const u64 h = xxh3::hash64(p.q + a, p.q_pos[i + 1] - a);
+  p.out[i] = (uint8_t)seekdev::bloom_probe(p.filter, p.filter_len, h);
 }
 
 // Bloom::from_keys (src/bloom.rs:48-70) for keys on the device: one thread per key sets its k
@@ -647,9 +525,9 @@ void launch_pack_ends(const PackLaunch& a, hipStream_t stream) {
 }
 
 void launch_seek(const SeekLaunch& a, hipStream_t stream) {
-  SeekParams p{a.fk, a.fk_pos, a.n_blocks, a.ext, a.data, a.ends, a.count, a.bstatus,
-               a.spill, a.spill_off, a.q, a.q_pos, a.n_q, a.out_block, a.out_entry,
-               a.out_status, a.out_valid, a.efirst};
+  SeekParams p{tpz_table{a.fk, a.fk_pos, a.ext, a.n_blocks, a.data, a.ends, a.count, a.bstatus,
+                         a.spill, a.spill_off, a.efirst},
+               a.q, a.q_pos, a.n_q, a.out_block, a.out_entry, a.out_status, a.out_valid};
   hipLaunchKernelGGL(seek_kernel, dim3((a.n_q + 255) / 256), dim3(256), 0, stream, p);
 }
 
