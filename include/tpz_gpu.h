@@ -68,7 +68,9 @@ extern "C" {
  *      path row claim, and TPZ_ERR_NOMEM of the host pipeline meaning a short caller buffer only
  *   8  batched point gets over resident tables: tpz_get_keys (LevelController::get's walk over
  *      L0 and the levels) and tpz_get_values (the gather of the values found), tpz_get_table,
- *      TPZ_GET_*; no existing struct or status changed
+ *      TPZ_GET_*; no existing struct or status changed. Same ABI, additive: tpz_scan_ranges and
+ *      tpz_scan_entries (LsmStorage::scan's SST half), TPZ_BOUND_*, TPZ_SCAN_*; a consumer tests
+ *      TPZ_HAS_SCAN
  * A consumer compiled against one header checks tpz_abi_version() == TPZ_ABI_VERSION. */
 #define TPZ_ABI_VERSION 8
 int tpz_abi_version(void);
@@ -742,6 +744,103 @@ tpz_err tpz_get_values(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n_t
                        uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
                        const uint32_t* d_block, const uint32_t* d_entry, const uint64_t* d_val_pos,
                        uint8_t* d_vals, uint64_t val_cap, void* stream);
+
+/* ---- batched LsmStorage::scan over resident tables ---------------------------------------
+ * The SST half of LsmStorage::scan(lower, upper) (src/lsm_storage.rs:335-374) for a batch of
+ * ranges, over the tables tpz_get_keys walks. Additive within ABI 8: new symbols and constants
+ * only (TPZ_HAS_SCAN tells a consumer the header has them). Per scan, with no memtables:
+ *   1. LevelController::level_tables_sorted (src/level.rs:538-579): L0 reversed (newest first),
+ *      then every level in stored order; that is the cursors' priority order. A table is dropped
+ *      iff biggest_key < the lower key (Included and Excluded alike) or smallest_key > the upper
+ *      key; Unbounded drops nothing. smallest_key is block_metas[0].first_key, biggest_key the
+ *      last entry's key of the last block (src/table.rs:143-151); both are resident already.
+ *   2. One SsTableIterator per surviving table: create_and_seek_to_key for Included,
+ *      create_and_seek_to_first for Unbounded; Excluded seeks and takes one next() when the
+ *      cursor is valid at an equal key. next() (src/table/iterator.rs:88-95) steps into the next
+ *      block when the block iterator ends, and that block's read can be an Err. A cursor is valid
+ *      iff its current key is non-empty.
+ *   3. MergeIterator (src/iterators/merge_iterator.rs:41-106) drops invalid cursors, yields the
+ *      smallest (key, priority), and on next advances every other cursor at an equal key first,
+ *      in increasing priority, until its key differs, then the current cursor once. An Err from
+ *      any of these steps ends the scan.
+ *   4. TwoMergeIterator with an always-invalid memtable side passes that sequence e0, e1, ..
+ *      through; the host merges its memtables over the device's output.
+ *   5. LsmIterator (src/lsm_iterator.rs): entries with an empty value are skipped; every element
+ *      AFTER e0, tombstones included, is tested against the end bound (Included stops at the
+ *      first key > upper, Excluded at the first key >= upper) and the first failure ends the scan.
+ *      e0 is never end-checked (LsmIterator::new, :22-33): over one table {a, d},
+ *      scan(Included(b), Included(c)) yields d. The device reproduces this.
+ *
+ * d_tables, h_level_first, n_levels: exactly tpz_get_keys', with its preconditions and its
+ * "unspecified, but bounded and clamped" clause for an unsorted level (and likewise for a table
+ * whose keys decrease). Bound keys are packed as for tpz_seek_keys (an Unbounded bound has an
+ * empty key); d_lo_kind / d_hi_kind hold one TPZ_BOUND_* byte per scan. `limit` >= 1 is the most
+ * entries a scan yields in this call, uniform per call; n_scans * limit < 2^32.
+ *
+ * tpz_scan_ranges, per scan i:
+ *   d_result[i]  TPZ_SCAN_DONE / MORE / ERROR
+ *   d_status[i]  TPZ_BLOCK_OK unless the result is ERROR
+ *   d_where[3i .. 3i+3)
+ *                the table (an index into d_tables), block and entry of the failure, as
+ *                tpz_get_keys reports them; 0xFFFFFFFF each unless the result is ERROR. A failure
+ *                while the cursors are created reports the first failing table in priority
+ *                order; one during a next, the first failing cursor in the order of step 3.
+ *   d_hit_table / d_hit_block / d_hit_entry [i * limit + j]
+ *                the j-th yielded entry (columns of n_scans * limit u32; the slots past a scan's
+ *                count are not written)
+ *   d_first, d_key_first, d_val_first
+ *                n_scans + 1 u64 each: the exclusive prefix sums of the scans' yielded entry
+ *                counts, key bytes and value bytes; on ERROR the count is the number of entries
+ *                yielded before the failing step
+ *   d_info       3 u64: the three totals, which the caller reads back once to size the gather
+ * A table the reference could not have opened (SsTable::open fails on it: no blocks, or a last
+ * block that cannot be read or whose first or last entry cannot) makes every scan an ERROR at
+ * that table, found by the filter and so before any seek: status MALFORMED, or the last block's
+ * status when its read is an Err; d_where block = the last block (0xFFFFFFFF without blocks),
+ * entry = 0xFFFFFFFF.
+ * Paging: TPZ_BOUND_AFTER as the lower kind means Excluded with the first merged element
+ * end-checked like every later one: it continues a scan that reported MORE from its last yielded
+ * key, and with every block readable the pages concatenate to the unpaged scan. It is not valid
+ * as an upper kind. Kinds live in device memory: an out-of-range kind gives that scan ERROR with
+ * TPZ_BLOCK_MALFORMED and d_where all 0xFFFFFFFF.
+ *
+ * tpz_scan_entries writes the yielded entries as a tpz_entries: d_kpos and d_vpos
+ * (d_first[n_scans] + 1 u64 each) and the packed key and value bytes (d_keys, d_vals 16-byte
+ * aligned); scan i owns entries [d_first[i], d_first[i+1]) in iterator order. Nothing is written
+ * at or past key_cap / val_cap; table, block and entry are checked against the descriptors.
+ *
+ * Both are asynchronous on `stream` and use the stream's grow-only workspace (tpz_scan_ranges:
+ * the cursors, 8 B per scan and table, plus a status byte each and the scans' partial sums).
+ * TPZ_ERR_INVALID_ARG, before any device work, for n_tables > TPZ_SCAN_MAX_TABLES (one wave
+ * merges a scan, a cursor per lane; lifting the limit is a later change), the h_level_first rules
+ * of tpz_get_keys, limit == 0, n_scans * limit >= 2^32, or null or misaligned pointers (u64
+ * columns 8-byte, u32 columns 4-byte, d_keys and d_vals 16-byte). n_scans == 0 and n_tables == 0
+ * are valid: with no tables every scan is DONE with nothing yielded. */
+#define TPZ_HAS_SCAN 1
+#define TPZ_SCAN_MAX_TABLES 64u
+#define TPZ_BOUND_UNBOUNDED 0
+#define TPZ_BOUND_INCLUDED 1
+#define TPZ_BOUND_EXCLUDED 2
+#define TPZ_BOUND_AFTER 3 /* lower only: see paging */
+#define TPZ_SCAN_DONE 0   /* the iterator became invalid within `limit` entries */
+#define TPZ_SCAN_MORE 1   /* `limit` entries yielded and the iterator is still valid */
+#define TPZ_SCAN_ERROR 2  /* the reference's Err / panic; d_status says which */
+
+tpz_err tpz_scan_ranges(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n_tables,
+                        const uint32_t* h_level_first, uint32_t n_levels,
+                        const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                        const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                        const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans,
+                        uint32_t limit, uint8_t* d_result, uint8_t* d_status, uint32_t* d_where,
+                        uint32_t* d_hit_table, uint32_t* d_hit_block, uint32_t* d_hit_entry,
+                        uint64_t* d_first, uint64_t* d_key_first, uint64_t* d_val_first,
+                        uint64_t* d_info, void* stream);
+tpz_err tpz_scan_entries(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n_tables,
+                         uint32_t n_scans, uint32_t limit, const uint32_t* d_hit_table,
+                         const uint32_t* d_hit_block, const uint32_t* d_hit_entry,
+                         const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
+                         uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
+                         void* stream);
 
 /* ---- host write side (inputs for benches and the table facade) ---------------------------
  * SsTableBuilder::add + block_build (src/table/builder.rs:49-85) with BlockBuilder's fill rule

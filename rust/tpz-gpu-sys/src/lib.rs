@@ -49,6 +49,21 @@ pub const TPZ_GET_FOUND: u8 = 1;
 pub const TPZ_GET_DELETED: u8 = 2;
 pub const TPZ_GET_ERROR: u8 = 3;
 
+/// The header declares `tpz_scan_ranges` / `tpz_scan_entries` (additive within ABI 8).
+pub const TPZ_HAS_SCAN: u32 = 1;
+/// One wave merges a scan, a cursor per lane.
+pub const TPZ_SCAN_MAX_TABLES: u32 = 64;
+/// `tpz_scan_ranges`' `d_lo_kind` / `d_hi_kind`, one byte per scan (`std::ops::Bound`; AFTER,
+/// lower only, continues a scan that reported MORE from its last yielded key).
+pub const TPZ_BOUND_UNBOUNDED: u8 = 0;
+pub const TPZ_BOUND_INCLUDED: u8 = 1;
+pub const TPZ_BOUND_EXCLUDED: u8 = 2;
+pub const TPZ_BOUND_AFTER: u8 = 3;
+/// `tpz_scan_ranges`' `d_result`, one byte per scan.
+pub const TPZ_SCAN_DONE: u8 = 0;
+pub const TPZ_SCAN_MORE: u8 = 1;
+pub const TPZ_SCAN_ERROR: u8 = 2;
+
 /// `tpz_batch`: blocks (or ranges, or files) back to back in HBM; block i is
 /// `d_src[d_ext[i] .. d_ext[i + 1])`.
 #[repr(C)]
@@ -250,6 +265,20 @@ extern "C" {
                           n_keys: u32, d_result: *const u8, d_table: *const u32,
                           d_block: *const u32, d_entry: *const u32, d_val_pos: *const u64,
                           d_vals: *mut u8, val_cap: u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_scan_ranges(ctx: *mut TpzCtx, d_tables: *const tpz_get_table, n_tables: u32,
+                           h_level_first: *const u32, n_levels: u32, d_lo_keys: *const u8,
+                           d_lo_pos: *const u64, d_lo_kind: *const u8, d_hi_keys: *const u8,
+                           d_hi_pos: *const u64, d_hi_kind: *const u8, n_scans: u32, limit: u32,
+                           d_result: *mut u8, d_status: *mut u8, d_where: *mut u32,
+                           d_hit_table: *mut u32, d_hit_block: *mut u32, d_hit_entry: *mut u32,
+                           d_first: *mut u64, d_key_first: *mut u64, d_val_first: *mut u64,
+                           d_info: *mut u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_scan_entries(ctx: *mut TpzCtx, d_tables: *const tpz_get_table, n_tables: u32,
+                            n_scans: u32, limit: u32, d_hit_table: *const u32,
+                            d_hit_block: *const u32, d_hit_entry: *const u32,
+                            d_first: *const u64, d_keys: *mut u8, key_cap: u64,
+                            d_kpos: *mut u64, d_vals: *mut u8, val_cap: u64, d_vpos: *mut u64,
+                            stream: *mut c_void) -> TpzErr;
     pub fn tpz_flat_entry_pos(ctx: *mut TpzCtx, cols: *const TpzFlatColumns, n_blocks: u32,
                               d_kpos: *mut u64, d_vpos: *mut u64, d_info: *mut u32,
                               stream: *mut c_void) -> TpzErr;

@@ -27,6 +27,9 @@ ABI_VERSION = 8           # TPZ_ABI_VERSION this binding was written against
 GET_MAX_LEVELS = 16       # TPZ_GET_MAX_LEVELS
 GET_ABSENT, GET_FOUND, GET_DELETED, GET_ERROR = range(4)   # tpz_get_keys' d_result (TPZ_GET_*)
 GET_NONE = 0xFFFFFFFF     # d_table / d_block / d_entry of a walk that ended nowhere
+SCAN_MAX_TABLES = 64      # TPZ_SCAN_MAX_TABLES
+BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED, BOUND_AFTER = range(4)   # TPZ_BOUND_*
+SCAN_DONE, SCAN_MORE, SCAN_ERROR = range(3)    # tpz_scan_ranges' d_result (TPZ_SCAN_*)
 MERGE_MAX_RUNS = 256      # TPZ_MERGE_MAX_RUNS
 MERGE_TILE = 1024         # entries per tile-merge workgroup of tpz_merge_runs (csrc kMergeTile)
 MERGE_LANE_COPY_MAX = 256  # longer keys / values are copied by the whole wave (csrc kLaneCopyMax)
@@ -212,6 +215,16 @@ def lib() -> C.CDLL:
         L.tpz_get_values.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + \
             [C.c_void_p] * 6 + [C.c_uint64, C.c_void_p]
         L.tpz_get_values.restype = C.c_int
+        if not hasattr(L, "tpz_scan_ranges"):     # (additive within ABI 8: an older build lacks it)
+            raise TpzError(f"{LIB_PATH} does not export tpz_scan_ranges: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_scan_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + \
+            [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 11
+        L.tpz_scan_ranges.restype = C.c_int
+        L.tpz_scan_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + \
+            [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                C.c_void_p]
+        L.tpz_scan_entries.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -535,6 +548,36 @@ class Context:
                                    C.c_void_p(d_result), C.c_void_p(d_table), C.c_void_p(d_block),
                                    C.c_void_p(d_entry), C.c_void_p(d_val_pos), C.c_void_p(d_vals),
                                    val_cap, C.c_void_p(stream)), "tpz_get_values")
+
+    def scan_ranges_ptrs(self, d_tables: int, n_tables: int, h_level_first: int, n_levels: int,
+                         d_lo_keys: int, d_lo_pos: int, d_lo_kind: int, d_hi_keys: int,
+                         d_hi_pos: int, d_hi_kind: int, n_scans: int, limit: int, d_result: int,
+                         d_status: int, d_where: int, d_hit_table: int, d_hit_block: int,
+                         d_hit_entry: int, d_first: int, d_key_first: int, d_val_first: int,
+                         d_info: int, stream: int = 0) -> None:
+        """tpz_scan_ranges: LsmStorage::scan's SST half (lsm_storage.rs:335-374) for every range
+        over the n_tables tpz_get_table descriptors at d_tables: the yielded entries' positions,
+        at most `limit` per scan."""
+        ptrs = [C.c_void_p(x) for x in (d_result, d_status, d_where, d_hit_table, d_hit_block,
+                                        d_hit_entry, d_first, d_key_first, d_val_first, d_info)]
+        check(lib().tpz_scan_ranges(self.handle, C.c_void_p(d_tables), n_tables,
+                                    C.c_void_p(h_level_first), n_levels, C.c_void_p(d_lo_keys),
+                                    C.c_void_p(d_lo_pos), C.c_void_p(d_lo_kind),
+                                    C.c_void_p(d_hi_keys), C.c_void_p(d_hi_pos),
+                                    C.c_void_p(d_hi_kind), n_scans, limit, *ptrs,
+                                    C.c_void_p(stream)), "tpz_scan_ranges")
+
+    def scan_entries_ptrs(self, d_tables: int, n_tables: int, n_scans: int, limit: int,
+                          d_hit_table: int, d_hit_block: int, d_hit_entry: int, d_first: int,
+                          d_keys: int, key_cap: int, d_kpos: int, d_vals: int, val_cap: int,
+                          d_vpos: int, stream: int = 0) -> None:
+        """tpz_scan_entries: the entries tpz_scan_ranges yielded, as a tpz_entries."""
+        check(lib().tpz_scan_entries(self.handle, C.c_void_p(d_tables), n_tables, n_scans, limit,
+                                     C.c_void_p(d_hit_table), C.c_void_p(d_hit_block),
+                                     C.c_void_p(d_hit_entry), C.c_void_p(d_first),
+                                     C.c_void_p(d_keys), key_cap, C.c_void_p(d_kpos),
+                                     C.c_void_p(d_vals), val_cap, C.c_void_p(d_vpos),
+                                     C.c_void_p(stream)), "tpz_scan_entries")
 
     def flat_entry_pos_ptrs(self, cols: dict, n_blocks: int, d_kpos: int, d_vpos: int,
                             d_info: int, stream: int = 0) -> None:

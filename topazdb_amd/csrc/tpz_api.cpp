@@ -143,6 +143,9 @@ struct tpz_workspace {
   size_t merge_cap = 0;
   void* d_get = nullptr;        // tpz_get_keys: the value-length scan's partial sums
   size_t get_cap = 0;
+  void* d_scan = nullptr;       // tpz_scan_ranges: cursors, their statuses, scan partial sums;
+                                // tpz_scan_entries: the scans' byte bases and partial sums
+  size_t scan_cap = 0;
   uint32_t* h_info = nullptr;   // pinned: tpz_plan_blocks' read-back of its 16-byte info
 };
 
@@ -171,6 +174,7 @@ void free_workspace(tpz_workspace& w) {
   if (w.d_comp) (void)hipFree(w.d_comp);
   if (w.d_merge) (void)hipFree(w.d_merge);
   if (w.d_get) (void)hipFree(w.d_get);
+  if (w.d_scan) (void)hipFree(w.d_scan);
   if (w.h_info) (void)hipHostFree(w.h_info);
   w = tpz_workspace{};
 }
@@ -1086,6 +1090,97 @@ tpz_err tpz_get_values(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tab
   tpz::GetGatherLaunch a{d_tables, n_tables, n_keys, d_result, d_table, d_block, d_entry,
                          d_val_pos, d_vals, val_cap};
   tpz::launch_get_gather(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+// limit >= 1 and n_scans * limit < 2^32 (the hit columns are indexed with it).
+static bool scan_shape_ok(uint32_t n_tables, uint32_t n_scans, uint32_t limit) {
+  return n_tables <= TPZ_SCAN_MAX_TABLES && limit != 0 &&
+         (uint64_t)n_scans * limit < (1ull << 32);
+}
+
+tpz_err tpz_scan_ranges(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
+                        const uint32_t* h_level_first, uint32_t n_levels,
+                        const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                        const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                        const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans,
+                        uint32_t limit, uint8_t* d_result, uint8_t* d_status, uint32_t* d_where,
+                        uint32_t* d_hit_table, uint32_t* d_hit_block, uint32_t* d_hit_entry,
+                        uint64_t* d_first, uint64_t* d_key_first, uint64_t* d_val_first,
+                        uint64_t* d_info, void* stream) {
+  if (!c || !d_lo_pos || !d_lo_kind || !d_hi_pos || !d_hi_kind || !d_result || !d_status ||
+      !d_where || !d_hit_table || !d_hit_block || !d_hit_entry || !d_first || !d_key_first ||
+      !d_val_first || !d_info || (n_tables && !d_tables))
+    return TPZ_ERR_INVALID_ARG;
+  if (!scan_shape_ok(n_tables, n_scans, limit) ||
+      !level_first_ok(h_level_first, n_levels, n_tables))
+    return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_tables | (uintptr_t)d_lo_pos | (uintptr_t)d_hi_pos | (uintptr_t)d_first |
+        (uintptr_t)d_key_first | (uintptr_t)d_val_first | (uintptr_t)d_info) & 7u) ||
+      (((uintptr_t)d_where | (uintptr_t)d_hit_table | (uintptr_t)d_hit_block |
+        (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_key_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_val_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_ranges_work_bytes(n_scans, n_tables));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_scan;
+  }
+  tpz::ScanLaunch a{d_tables, n_tables, n_levels ? h_level_first[1] : 0u, d_lo_keys, d_lo_pos,
+                    d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit, d_result, d_status,
+                    d_where, d_hit_table, d_hit_block, d_hit_entry, d_first, d_key_first,
+                    d_val_first, d_info, work};
+  tpz::launch_scan_ranges(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_scan_entries(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
+                         uint32_t n_scans, uint32_t limit, const uint32_t* d_hit_table,
+                         const uint32_t* d_hit_block, const uint32_t* d_hit_entry,
+                         const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
+                         uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
+                         void* stream) {
+  if (!c || !d_kpos || !d_vpos || (n_tables && !d_tables) || (key_cap && !d_keys) ||
+      (val_cap && !d_vals) ||
+      (n_scans && (!d_hit_table || !d_hit_block || !d_hit_entry || !d_first)))
+    return TPZ_ERR_INVALID_ARG;
+  if (!scan_shape_ok(n_tables, n_scans, limit)) return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
+      (((uintptr_t)d_tables | (uintptr_t)d_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u) ||
+      (((uintptr_t)d_hit_table | (uintptr_t)d_hit_block | (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_entries_work_bytes(n_scans));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_scan;
+  }
+  tpz::ScanEntriesLaunch a{d_tables, n_tables, n_scans, limit, d_hit_table, d_hit_block,
+                           d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals, val_cap, d_vpos,
+                           work};
+  tpz::launch_scan_entries(a, s);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }

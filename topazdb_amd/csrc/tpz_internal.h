@@ -368,6 +368,54 @@ struct GetGatherLaunch {
 };
 void launch_get_gather(const GetGatherLaunch& a, hipStream_t stream);
 
+// tpz_scan_ranges / tpz_scan_entries (tpz_scan.hip): LsmStorage::scan's SST half over resident
+// tables.
+struct ScanLaunch {
+  const tpz_get_table* tabs;    // device
+  uint32_t n_tables;            // <= TPZ_SCAN_MAX_TABLES
+  uint32_t l0;                  // the number of L0 tables (h_level_first[1], or 0)
+  const uint8_t* lo;
+  const uint64_t* lo_pos;
+  const uint8_t* lo_kind;
+  const uint8_t* hi;
+  const uint64_t* hi_pos;
+  const uint8_t* hi_kind;
+  uint32_t n_scans;             // > 0
+  uint32_t limit;               // > 0, n_scans * limit < 2^32
+  uint8_t* result;
+  uint8_t* status;
+  uint32_t* where;              // 3 x n_scans
+  uint32_t* hit_table;          // n_scans x limit each
+  uint32_t* hit_block;
+  uint32_t* hit_entry;
+  uint64_t* first;              // n_scans + 1 each: the counts and byte totals, scanned in place
+  uint64_t* key_first;
+  uint64_t* val_first;
+  uint64_t* info;               // 3 u64
+  void* work;                   // scan_ranges_work_bytes(n_scans, n_tables) of device scratch
+};
+uint64_t scan_ranges_work_bytes(uint32_t n_scans, uint32_t n_tables);
+void launch_scan_ranges(const ScanLaunch& a, hipStream_t stream);
+struct ScanEntriesLaunch {
+  const tpz_get_table* tabs;
+  uint32_t n_tables;
+  uint32_t n_scans;             // > 0
+  uint32_t limit;
+  const uint32_t* hit_table;
+  const uint32_t* hit_block;
+  const uint32_t* hit_entry;
+  const uint64_t* first;
+  uint8_t* keys;
+  uint64_t key_cap;
+  uint64_t* kpos;
+  uint8_t* vals;
+  uint64_t val_cap;
+  uint64_t* vpos;
+  void* work;                   // scan_entries_work_bytes(n_scans) of device scratch
+};
+uint64_t scan_entries_work_bytes(uint32_t n_scans);
+void launch_scan_entries(const ScanEntriesLaunch& a, hipStream_t stream);
+
 // tpz_compress_blocks (tpz_compress.hip): scratch bytes for the per-block slots; the snappy
 // encode, the scan of the sizes into dst_ext and the packing into dst.
 uint64_t compress_scratch_bytes(uint64_t src_bytes, uint32_t n_blocks);

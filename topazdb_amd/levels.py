@@ -1,4 +1,5 @@
-"""LevelController::get (src/level.rs:427-465) for batches of keys over tables resident in HBM.
+"""LevelController::get (src/level.rs:427-465) and the SST half of LsmStorage::scan
+(src/lsm_storage.rs:335-374) for batches of keys and ranges over tables resident in HBM.
 
 `DeviceLevels(ctx, levels)` takes the level lists of a LevelController (`levels[0]` is L0 in push
 order, oldest first; every level below is sorted by smallest key) whose tables were opened with
@@ -10,7 +11,15 @@ descriptor per table once, and answers
   get(key)          the reference's Result<Option<Bytes>>: bytes, None, or the reference's error
                     (BlockError) / panic (ReferencePanic)
 
-There is no CPU fallback: the walk and the gather are the kernels of csrc/tpz_get.hip.
+  scan_batch(ranges, limit)
+                    one tpz_scan_ranges (the table filter, one cursor per table, MergeIterator,
+                    the end bound and the tombstone rule, at most `limit` entries per range), one
+                    read-back of the totals, one tpz_scan_entries
+  scan(lower, upper)
+                    the reference's FusedIterator<LsmIterator>, pulled page by page
+
+There is no CPU fallback: the walk, the merge and the gathers are the kernels of csrc/tpz_get.hip
+and csrc/tpz_scan.hip.
 """
 from __future__ import annotations
 
@@ -20,13 +29,75 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (BLOCK_MALFORMED, GET_ABSENT, GET_DELETED, GET_ERROR, GET_FOUND, GET_NONE,
+from ._lib import (BLOCK_MALFORMED, BOUND_AFTER, BOUND_EXCLUDED, BOUND_INCLUDED, BOUND_UNBOUNDED,
+                   GET_ABSENT, GET_DELETED, GET_ERROR, GET_FOUND, GET_NONE, SCAN_ERROR, SCAN_MORE,
                    Context, GetTable)
 from .table import DeviceTable, ReferencePanic, _pack
 
 
 def _device_table(t) -> DeviceTable:
     return t if isinstance(t, DeviceTable) else t.device
+
+
+_KINDS = {"in": BOUND_INCLUDED, "ex": BOUND_EXCLUDED, "after": BOUND_AFTER}
+
+
+def _bound(b, lower: bool) -> tuple[int, bytes]:
+    """None / ("in", key) / ("ex", key) / ("after", key) -> (TPZ_BOUND_*, key)."""
+    if b is None:
+        return BOUND_UNBOUNDED, b""
+    kind, key = b
+    if kind not in _KINDS or (kind == "after" and not lower):
+        raise ValueError(f"bound kind {kind!r}")
+    return _KINDS[kind], bytes(key)
+
+
+class ScanIterator:
+    """FusedIterator<LsmIterator> (src/lsm_iterator.rs) over DeviceLevels.scan_batch pages: a
+    page that reported MORE is continued from its last key with ("after", key); a page that
+    reported ERROR raises the reference's error once the entries before the failure are
+    consumed."""
+
+    def __init__(self, levels: "DeviceLevels", lower, upper, page: int):
+        self._levels, self._upper, self._page = levels, upper, page
+        self._pull(lower)
+
+    def _pull(self, lower) -> None:
+        r = self._levels.scan_batch([(lower, self._upper)], self._page)
+        kp, vp = r["kpos"].astype(np.int64), r["vpos"].astype(np.int64)
+        self._ents = [(r["keys"][kp[j]:kp[j + 1]], r["values"][vp[j]:vp[j + 1]])
+                      for j in range(int(r["first"][1]))]
+        self._j = 0
+        self._result = int(r["result"][0])
+        self._fail = (int(r["status"][0]), *(int(x) for x in r["where"][0]))
+        if not self._ents:
+            self._end()
+
+    def _end(self) -> None:
+        """The page is used up: the next one, the reference's error, or the end."""
+        if self._result == SCAN_ERROR:
+            self._result = None
+            if self._fail[2] == GET_NONE:        # a table without blocks: block_metas[0]
+                raise ReferencePanic("index out of bounds: the len is 0 but the index is 0")
+            raise self._levels.error(*self._fail)
+        if self._result == SCAN_MORE:
+            self._pull(("after", self._ents[-1][0]))
+
+    def is_valid(self) -> bool:
+        return self._j < len(self._ents)
+
+    def key(self) -> bytes:
+        return self._ents[self._j][0]
+
+    def value(self) -> bytes:
+        return self._ents[self._j][1]
+
+    def next(self) -> None:
+        if not self.is_valid():              # FusedIterator::next
+            return
+        self._j += 1
+        if self._j == len(self._ents):
+            self._end()
 
 
 class DeviceLevels:
@@ -100,6 +171,84 @@ class DeviceLevels:
         out["val_pos"] = w["val_pos"].cpu().numpy().astype(np.uint64)
         out["values"] = vals.cpu().numpy().tobytes()
         return out
+
+    def scan_ranges(self, ranges: list, limit: int) -> dict:
+        """tpz_scan_ranges on the current stream: device tensors result, status (uint8), where
+        (int32, n x 3), hit_table, hit_block, hit_entry (int32, n x limit), first, key_first,
+        val_first (int64, n + 1), info (int64, 3), and n, limit."""
+        n = len(ranges)
+        lo = [_bound(r[0], True) for r in ranges]
+        hi = [_bound(r[1], False) for r in ranges]
+        dev = self.dev
+        cols = []
+        for side in (lo, hi):
+            buf, pos = _pack([k for _, k in side])
+            cols += [torch.from_numpy(buf.copy()).to(dev), torch.from_numpy(pos).to(dev),
+                     torch.from_numpy(np.array([k for k, _ in side] or [0], np.uint8)).to(dev)]
+        out = {k: torch.empty(max(n, 1), dtype=torch.uint8, device=dev) for k in ("result", "status")}
+        out["where"] = torch.empty((max(n, 1), 3), dtype=torch.int32, device=dev)
+        for k in ("hit_table", "hit_block", "hit_entry"):
+            out[k] = torch.empty(max(n * limit, 1), dtype=torch.int32, device=dev)
+        for k in ("first", "key_first", "val_first"):
+            out[k] = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        out["info"] = torch.empty(3, dtype=torch.int64, device=dev)
+        self.ctx.scan_ranges_ptrs(self.d_tables.data_ptr(), self.n_tables,
+                                  self.level_first.ctypes.data, self.n_levels,
+                                  *(c.data_ptr() for c in cols), n, limit,
+                                  *(out[k].data_ptr() for k in
+                                    ("result", "status", "where", "hit_table", "hit_block",
+                                     "hit_entry", "first", "key_first", "val_first", "info")),
+                                  torch.cuda.current_stream(dev).cuda_stream)
+        out["n"], out["limit"] = n, limit
+        out["_bounds"] = cols        # alive until the stream has run the scan
+        return out
+
+    def scan_entries(self, s: dict, totals) -> dict:
+        """tpz_scan_entries on the current stream over scan_ranges' outputs: device tensors kpos,
+        vpos (int64, entries + 1), keys, values (uint8). totals = the three numbers of info."""
+        n_ent, kbytes, vbytes = (int(x) for x in totals)
+        dev = self.dev
+        out = {"kpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
+               "vpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
+               "keys": torch.empty(max(kbytes, 1), dtype=torch.uint8, device=dev),
+               "values": torch.empty(max(vbytes, 1), dtype=torch.uint8, device=dev)}
+        self.ctx.scan_entries_ptrs(self.d_tables.data_ptr(), self.n_tables, s["n"], s["limit"],
+                                   s["hit_table"].data_ptr(), s["hit_block"].data_ptr(),
+                                   s["hit_entry"].data_ptr(), s["first"].data_ptr(),
+                                   out["keys"].data_ptr(), kbytes, out["kpos"].data_ptr(),
+                                   out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
+                                   torch.cuda.current_stream(dev).cuda_stream)
+        out["keys"], out["values"] = out["keys"][:kbytes], out["values"][:vbytes]
+        return out
+
+    def scan_batch(self, ranges: list, limit: int) -> dict:
+        """LsmStorage::scan's SST half for every (lower, upper) of `ranges`, at most `limit`
+        entries each; a bound is None (Unbounded), ("in", key), ("ex", key) or, as a lower bound
+        only, ("after", key). Numpy arrays: result (SCAN_DONE / SCAN_MORE / SCAN_ERROR), status,
+        where (n x 3 uint32: table, block, entry of a failure, GET_NONE otherwise), hit_table,
+        hit_block, hit_entry (n x limit uint32; a row is defined up to the scan's count), first,
+        key_first, val_first (n + 1 uint64); kpos, vpos (entries + 1 uint64) and keys, values
+        (bytes): scan i owns entries [first[i], first[i + 1]) in iterator order, entry j's key
+        is keys[kpos[j]:kpos[j + 1]]."""
+        s = self.scan_ranges(ranges, limit)
+        n = s["n"]
+        totals = s["info"].cpu().numpy()             # the one read-back between the two calls
+        e = self.scan_entries(s, totals)
+        out = {k: s[k][:n].cpu().numpy() for k in ("result", "status")}
+        out["where"] = s["where"][:n].cpu().numpy().view(np.uint32)
+        for k in ("hit_table", "hit_block", "hit_entry"):
+            out[k] = s[k][:n * limit].cpu().numpy().view(np.uint32).reshape(n, limit)
+        for k in ("first", "key_first", "val_first"):
+            out[k] = s[k].cpu().numpy().astype(np.uint64)
+        for k in ("kpos", "vpos"):
+            out[k] = e[k].cpu().numpy().astype(np.uint64)
+        out["keys"] = e["keys"].cpu().numpy().tobytes()
+        out["values"] = e["values"].cpu().numpy().tobytes()
+        return out
+
+    def scan(self, lower=None, upper=None, page: int = 256) -> ScanIterator:
+        """lsm_storage.rs:335-374 without memtables: is_valid() / key() / value() / next()."""
+        return ScanIterator(self, lower, upper, page)
 
     def _host_block(self, table: int, block: int):
         t = self.tables[table]
