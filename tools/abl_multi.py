@@ -106,7 +106,8 @@ def main():
         t = sorted(times[v])
         out = {"variant": v, "ms_median": round(t[len(t) // 2], 4), "ms_min": round(t[0], 4),
                "gib_s_median": round(in_gib / (t[len(t) // 2] * 1e-3), 1),
-               "equals_full": same.get(v)}
+               "equals_full": same.get(v), "ms_max": round(t[-1], 4),
+               "ms_rounds": [round(x, 4) for x in times[v]], "config": a.config}
         if v == "stamps":
             L, h = libs[v]
             L.tpz_debug_stamps.argtypes = [C.c_void_p, C.c_int]

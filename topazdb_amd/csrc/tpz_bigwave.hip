@@ -595,7 +595,10 @@ __device__ __forceinline__ u32 bigwave_phase(const BWParams& p, uint8_t* lds, u3
         const u32 vs = (ktot + 15) & ~15u;                                     // tpz_value_start
         const bool slots_fit = 6u * n <= len;
         // the {kend, vend} pairs, whole 128-byte lines (pairs past n are zero)
-        uint2* ends_g = reinterpret_cast<uint2*>(p.ends) + ends_base(p.efirst, s, b);
+        // (exact ends: a scalar load. As a vector load its wait was vmcnt(0), placed on the
+        // slotted arm too, which drained the previous block's copy stores.)
+        uint2* ends_g = reinterpret_cast<uint2*>(p.ends) +
+                        (p.efirst ? ld_uniform(p.efirst, b) : entry_base(s, b));
         if (slots_fit && lane < (p.efirst ? n : (n + 15) & ~15u))
           ends_g[lane] = act ? make_uint2(ki, vi) : make_uint2(0, 0);
         if (bad || !slots_fit || (u64)vs + vtot > (u64)len + 2) {

@@ -534,9 +534,26 @@ __device__ __forceinline__ void put_meta(const Out& o, u32 b, u32 st, u32 n, u32
   __builtin_amdgcn_raw_buffer_store_b32(n, whole_rsrc(o.count), l0 ? 4 * b : kOob, 0, 0);
   __builtin_amdgcn_raw_buffer_store_b32(crc, whole_rsrc(o.crc), l0 ? 4 * b : kOob, 0, 0);
 }
-// (Zero-length stores issued after the prefetch loads, so that the compiler's wait for them
-// became vmcnt(>= K) on every path, measured 0.5-1.5 % slower than none: profiles/r1/
-// ablations_vmpad.jsonl, profiles/r4/vmpad/.)
+// Padding stores: K out-of-range stores (dropped by the descriptor's range check: no traffic)
+// issued straight after the wave loop's prefetch loads. The loop waits for those loads at its
+// top, one block later; vmcnt counts loads and stores in issue order, and the compiler waits
+// vmcnt(N) with N = the fewest operations any path issues after the load. Without padding some
+// path (a long block, a rejected one) issues none, the wait is vmcnt(0), and it also waits for
+// the acknowledgement of the block's own copy stores, issued moments before. With K stores on
+// every path it is vmcnt(K): the block's last K stores stay in flight into the next block.
+// (Round 4 measured such a build 0.5-1.5 % slower, profiles/r4/vmpad/; it still waited vmcnt(0)
+// in the parse and at the loop's latch, so the relaxed wait bought nothing. DESIGN 4g.)
+// (The hot path stores 8 times per block: the ends, 3 x meta, 4 windows. 4 measured 1.733 /
+// 1.735 ms per 2^20 4k blocks, 8 1.735 / 1.741, 0 1.743 / 1.742, the parent 1.762 / 1.759:
+// profiles/prefetch/ab_4k_pads_*.jsonl.)
+constexpr int kVmPad = 4;
+template <int K>
+__device__ __forceinline__ void vm_pad(__amdgpu_buffer_rsrc_t rs) {
+  // (distinct, non-adjacent offsets: equal ones are merged into one store, adjacent ones into a
+  // wider one)
+#pragma unroll
+  for (int k = 0; k < K; k++) __builtin_amdgcn_raw_buffer_store_b32(0u, rs, kOob - 64u * k, 0, 0);
+}
 
 // Bytes [lo, hi) of the 4-byte word d (lo, hi in 0..16, relative to the chunk start).
 __device__ __forceinline__ u32 byte_mask(int lo, int hi, int d) {
@@ -1308,10 +1325,11 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
     const u32 dl = P - 2 - 2 * n;
     // (flat: the exact ends, n pairs reserved for every block by tpz_flat_layout)
     const bool slots_fit = FLAT || 6u * n <= len;
-    // (flat: ef = efirst[b], loaded with the block's prefetch)
+    // (flat and exact ends: ef = efirst[b], a scalar load issued with the block's prefetch; no
+    // memory access here, so nothing in the parse waits on vmcnt)
     // (uniform: readfirstlane'd, so that the store's descriptor is built in SGPRs; the compiler
     // could not tell and wrapped the store in a waterfall loop)
-    uint2* ends_g = reinterpret_cast<uint2*>(o.ends) + uni64(FLAT ? ef : ends_base(o.efirst, ext_b, b));
+    uint2* ends_g = reinterpret_cast<uint2*>(o.ends) + uni64((FLAT || o.efirst) ? ef : entry_base(ext_b, b));
     // whole 128-byte lines of {kend, vend} in the slotted layout; exactly n in the exact one
     const u32 n_pad = o.efirst ? n : (n + 15) & ~15u;
     {
@@ -1832,34 +1850,53 @@ void decode_wave_kernel(Params p) {
   // prefetch state for block b
   uint4 v[kWinRounds];
   u64 s_cur = 0, e_cur = 0;
-  u64 kf_cur = 0, vf_cur = 0, ef_cur = 0;   // flat: the block's column and ends starts, loaded
-                                             // one block ahead
+  u64 kf_cur = 0, vf_cur = 0, ef_cur = 0;   // the block's column starts (flat) and ends start (flat
+                                             // and exact ends), loaded one block ahead
   auto issue = [&](u32 bb, u32 jj, u64& s, u64& e) {
-    if (bb >= p.n_blocks) return;
-    if (FLAT) {   // (scalar loads: uniform, and no VGPRs held across the block)
-      kf_cur = const_load(p.out.kfirst, bb);
-      vf_cur = const_load(p.out.vfirst, bb);
-      ef_cur = const_load(p.out.efirst, bb);
+    // (The flat kernel keeps its two early returns, here and below: its loop is as it was.
+    // Without them its <true, 0> instance spills 223 SGPRs and takes scratch, and with the
+    // second alone it measured 0.5-1 % slower, profiles/prefetch/ab_flat4k_*.)
+    if (FLAT && bb >= p.n_blocks) return;
+    if (bb < p.n_blocks) {   // (past the batch the loop ends: the stale values are never used)
+      if (FLAT) {   // (scalar loads: uniform, and no VGPRs held across the block)
+        kf_cur = const_load(p.out.kfirst, bb);
+        vf_cur = const_load(p.out.vfirst, bb);
+        ef_cur = const_load(p.out.efirst, bb);
+      } else if (p.out.efirst) {
+        // exact ends: the block's first pair, a scalar load as well. (A vector load in the parse
+        // made the compiler wait vmcnt(0) there on every block, in the slotted layout too: both
+        // arms of the select wrote one register pair. That drained this prefetch and the
+        // previous block's stores: one exposed HBM round trip per block.)
+        ef_cur = const_load(p.out.efirst, bb);
+      }
     }
     s = lane64(gs_cur, jj);
     e = lane64(gs_cur, jj + 1);
-    const u64 len = e - s;
-    if (len > kWaveMaxLen) return;
+    // a block past the batch or too long for the wave path (decoded elsewhere): the same five
+    // loads through an empty descriptor, which fetch nothing. Every path then issues the same
+    // vector-memory operations and the loads' registers are written on every path (an early
+    // return made the compiler copy them at the merge, behind a wait for the loads).
+    const bool take = bb < p.n_blocks && e - s <= kWaveMaxLen;
+    if (FLAT && !take) return;
     const u64 ws = s & ~15ull;
     const u32 nbytes = (u32)(e - ws);
     const u32 rounds = (nbytes + 1023) >> 10;
     // the descriptor ends at the block's last 16-byte piece: lanes past it fetch nothing (the
     // next block's bytes are loaded once, by the wave that decodes it)
     const u64 e16 = (e + 15) & ~(u64)15;
-    const u64 lim = p.src_bytes < e16 ? p.src_bytes : e16;
-    __amdgpu_buffer_rsrc_t rs = window_rsrc(p.src, lim, ws);
+    const u64 lim = !take ? 0 : p.src_bytes < e16 ? p.src_bytes : e16;
+    __amdgpu_buffer_rsrc_t rs = window_rsrc(p.src, lim, take ? ws : 0);
     // all five loads unconditionally: the descriptor drops the pieces past the block (no
     // traffic), and the loads issue back to back with no branch between them (measured 2.3 %
     // faster than loading only the block's rounds, profiles/r2/ablations.jsonl)
 #pragma unroll
     for (int r = 0; r < kWinRounds; r++)
       v[r] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (u32)(r * 1024 + lane * 16), 0, 0));
-    if (e + 16 > p.src_bytes) {
+    // (through the window's descriptor, which is in SGPRs already; it spans lim - ws <=
+    // kWaveMaxLen + 30 bytes, or none: every padding offset is far outside it)
+    static_assert(kWaveMaxLen + 64 < kOob - 64u * kVmPad, "padding stores stay out of range");
+    vm_pad<FLAT ? 0 : kVmPad>(rs);
+    if (take && e + 16 > p.src_bytes) {
 #pragma unroll
       for (int r = 0; r < kWinRounds; r++)
         if ((u32)r < rounds) fix_tail(v[r], p.src, ws + r * 1024 + lane * 16, p.src_bytes);
@@ -2053,7 +2090,9 @@ __device__ __forceinline__ void big_block(const Params& p, const u32* tab, uint8
   } else {
     const u32 db = a0 + 2 + 2 * n, dl = P - 2 - 2 * n;
     const bool slots_fit = 6u * n <= len;
-    uint2* ends_g = reinterpret_cast<uint2*>(o.ends) + uni64(ends_base(o.efirst, ext_b, b));
+    // (exact ends: a scalar load, as in the wave path; no vmcnt wait on the slotted arm)
+    uint2* ends_g = reinterpret_cast<uint2*>(o.ends) +
+                    uni64(o.efirst ? const_load(o.efirst, b) : entry_base(ext_b, b));
     const u32 n_pad = o.efirst ? n : (n + 15) & ~15u;
     const u32 G = (n + 63) >> 6;
     // pass 1: group sums (read back by the same wave when there is one group)
