@@ -25,6 +25,10 @@
  *                           drives it (src/iterators/merge_iterator.rs:41-106, src/level.rs:178-222)
  *   tpz_get_keys +          LevelController::get (src/level.rs:427-465) for a batch of keys over
  *   tpz_get_values          tables resident in HBM: the walk over L0 and the levels, then the values
+ *   tpz_entries_bound +     do_compact around the merge (src/level.rs:133-222): sub_compact's key
+ *   tpz_table_cut +         range, SsTableBuilder::reach_capacity's table cuts (src/table/
+ *   tpz_sst_finish          builder.rs:88-94) and SsTableBuilder::build + FileObject::create's
+ *                           file bytes (builder.rs:97-141, src/table/file_object.rs:33-48)
  *
  * Plain pointers and sizes only. Pointers named d_* are device (HBM) pointers of the context's
  * device; h_* are host pointers. `stream` is a hipStream_t passed as void* (NULL = default).
@@ -70,7 +74,9 @@ extern "C" {
  *      L0 and the levels) and tpz_get_values (the gather of the values found), tpz_get_table,
  *      TPZ_GET_*; no existing struct or status changed. Same ABI, additive: tpz_scan_ranges and
  *      tpz_scan_entries (LsmStorage::scan's SST half), TPZ_BOUND_*, TPZ_SCAN_*; a consumer tests
- *      TPZ_HAS_SCAN
+ *      TPZ_HAS_SCAN. Same ABI, additive: tpz_entries_bound, tpz_table_cut, tpz_sst_finish and
+ *      tpz_sst_image_bytes (a compaction task's key ranges, table cuts and SST file images),
+ *      tpz_sst_image, TPZ_CUT_*; a consumer tests TPZ_HAS_TABLES
  * A consumer compiled against one header checks tpz_abi_version() == TPZ_ABI_VERSION. */
 #define TPZ_ABI_VERSION 8
 int tpz_abi_version(void);
@@ -841,6 +847,104 @@ tpz_err tpz_scan_entries(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n
                          const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
                          uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
                          void* stream);
+
+/* ---- a whole compaction task's output tables ----------------------------------------------
+ * What do_compact (src/level.rs:133-222) does around the merge and the block loop: the key ranges
+ * of its sub-compactions, SsTableBuilder's table cuts and the bytes of every output file. Additive
+ * within ABI 8: new symbols and constants only (TPZ_HAS_TABLES tells a consumer the header has
+ * them). The caller merges the task's input tables once (tpz_merge_runs) and then, per range and
+ * per output table, plans a window of blocks, cuts it, encodes it at the table's image start and
+ * finishes the images.
+ *
+ * tpz_entries_bound replaces sub_compact's seeks and its key_vaild test (src/level.rs:188-206:
+ * SsTableIterator::create_and_seek_to_key(table, lower) on every input, `iter.key() <= key` for an
+ * Included upper, `<` for an Excluded one), over the merged entries: d_out[i] = the number of
+ * entries whose key is < probe i, or <= probe i where d_inclusive[i] != 0. A range's entries are
+ * [bound(lower, 0), bound(upper, upper is Included)). Keys compare as Rust's [u8] Ord (bytewise,
+ * unsigned, a proper prefix first). Probe keys are packed as for tpz_seek_keys. That equals seeking
+ * every input and merging provided every input table's keys are strictly increasing
+ * (BlockIterator::seek_to_key returns any equal position otherwise): a precondition. On entries
+ * that are not sorted the counts are unspecified, but every loop is bounded and every index
+ * clamped. TPZ_ERR_INVALID_ARG, before any device work, for null or misaligned pointers (u64
+ * positions 8-byte, d_out 4-byte). n_probes == 0 is valid. Asynchronous on `stream`.
+ *
+ * tpz_table_cut replaces reach_capacity() in sub_compact's inner loop (src/level.rs:209,
+ * src/table/builder.rs:27,88-94: data.len() + 2 * meta.len() >= capacity, tested before each add;
+ * the size only changes when add() builds a block, builder.rs:54-57). `entries` are the merged
+ * entries; the table starts at entry `start`, and [start, start + win_entries) is the window that
+ * tpz_plan_blocks_async planned as its own tpz_entries (d_kpos + start, d_vpos + start,
+ * n_entries = win_entries) into d_first / d_ext / d_plan_info; the window ends at or before
+ * seg_end, the end of the sub-compaction's range. d_cut_ext holds the stored extents of the
+ * window's blocks, the ones the capacity is tested against: d_ext itself for Uncompress,
+ * tpz_compress_blocks' extents for Snappy / Lz4. With e_j = the first entry of block j, the cut is
+ * the smallest k with d_cut_ext[k + 1] + 2 (k + 1) >= capacity and e_{k+1} inside the window (the
+ * window's last block may be cut short by the window, so it never counts). The table then holds
+ * blocks 0..k and one more block with e_{k+1} alone (the add that built block k put it into a
+ * fresh block before the loop tested the size again), and the next table starts at e_{k+1} + 1.
+ * The call patches d_first[k + 2], d_ext[k + 2] (the closed form of the plan: entry bytes + 2 per
+ * entry + 7 per block) and d_plan_info[2] = k + 2, so that tpz_encode_blocks_async writes exactly
+ * the table. Without a cut the plan is left alone: a window that ends at seg_end is then the whole
+ * table, a shorter one has to be planned again over the window the call proposes.
+ *   d_cut  8 u64: [0] TPZ_CUT_NONE / FOUND / BAD_ENTRY, [1] k (BAD_ENTRY: the rejected entry, an
+ *          index into `entries`), [2] the table's blocks, [3] its entries, [4] its Uncompress
+ *          data bytes (d_ext at its block count), [5] the sum of its blocks' first-key lengths,
+ *          [6] where the next window starts (FOUND: the next table; else `start`), [7] where it
+ *          ends: the first entry by which its raw bytes (4 + key + value per entry) reach
+ *          capacity + block_size, which always holds the cut for Uncompress, or twice the bytes of
+ *          the window that held no cut plus that; clamped to seg_end.
+ * win_entries == 0 plans nothing (the plan pointers may be NULL): the call only proposes the
+ * window of a table starting at `start`. One workgroup; asynchronous on `stream`.
+ * TPZ_ERR_INVALID_ARG, before any device work, for null or misaligned pointers, capacity 0 (the
+ * reference then builds a table of no entries and panics on it), a block size outside
+ * tpz_plan_blocks' range, or start + win_entries > seg_end or seg_end > n_entries.
+ *
+ * tpz_sst_finish replaces SsTableBuilder::build (src/table/builder.rs:97-141) and
+ * FileObject::create's checksum (src/table/file_object.rs:33-48) for n_images tables whose data
+ * regions already sit at their image starts:
+ *   data | metas (BE u32 offset, BE u16 key length, key; src/table.rs:33-46) | BE u32 meta offset
+ *        | [Bloom::encode | BE u32 bloom offset] | BE u32 CRC-32 of everything before it
+ * The bloom section is there iff the descriptor has a filter (the caller builds one iff
+ * false_positive_rate.is_sign_positive(), builder.rs:111; the reference's own SsTable::open
+ * misreads a file without one, src/table.rs:75-87). d_images: n_images descriptors in DEVICE
+ * memory, in increasing address order, all inside [d_base, d_base + span_bytes): one allocation,
+ * because the CRC runs over the span as one batch of ranges and reads (never writes) the bytes
+ * between two images. max_blocks bounds every descriptor's n_blocks. A descriptor that breaks
+ * these rules is skipped and reports size 0.
+ *   d_info  4 u64 per image: {size (CRC trailer included), meta offset, bloom offset or
+ *           UINT64_MAX, the CRC}
+ * Asynchronous on `stream`; uses the stream's workspace (the key-length scan's partial sums, the
+ * CRC's ranges and accumulators). TPZ_ERR_INVALID_ARG, before any device work, for null or
+ * misaligned pointers (descriptors and d_info 8-byte) or span_bytes past 2^35. n_images == 0 is
+ * valid. tpz_sst_image_bytes (host) is the size such an image has. */
+#define TPZ_HAS_TABLES 1
+#define TPZ_CUT_NONE 0      /* no cut inside the window */
+#define TPZ_CUT_FOUND 1
+#define TPZ_CUT_BAD_ENTRY 2 /* the window's plan rejected an entry (tpz_plan_blocks_async's d_info[1]) */
+/* (declared with a tag, as tpz_get_table is) */
+struct tpz_sst_image {
+  uint8_t* d_image;        /* the image's first byte; its data region is there already */
+  uint64_t data_bytes;     /* the data region's length: the meta offset */
+  const uint32_t* d_first; /* n_blocks: each block's first entry, relative to entry_base */
+  const uint64_t* d_ext;   /* n_blocks: each block's offset in the data region */
+  uint32_t n_blocks;
+  uint32_t entry_base;     /* the table's first entry in `entries` */
+  const uint8_t* d_filter; /* Bloom::encode (tpz_bloom_build's 4-byte aligned output), or NULL */
+  uint64_t filter_len;
+};
+typedef struct tpz_sst_image tpz_sst_image;
+
+tpz_err tpz_entries_bound(tpz_ctx* ctx, const tpz_entries* entries, const uint8_t* d_keys,
+                          const uint64_t* d_key_pos, const uint8_t* d_inclusive,
+                          uint32_t n_probes, uint32_t* d_out, void* stream);
+tpz_err tpz_table_cut(tpz_ctx* ctx, const tpz_entries* entries, uint32_t start,
+                      uint32_t win_entries, uint32_t seg_end, uint32_t* d_first, uint64_t* d_ext,
+                      const uint64_t* d_cut_ext, uint32_t* d_plan_info, uint32_t block_size,
+                      uint64_t capacity, uint64_t* d_cut, void* stream);
+uint64_t tpz_sst_image_bytes(uint64_t data_bytes, uint64_t n_blocks, uint64_t first_key_bytes,
+                             uint64_t filter_len);
+tpz_err tpz_sst_finish(tpz_ctx* ctx, const tpz_entries* entries, const tpz_sst_image* d_images,
+                       uint32_t n_images, uint32_t max_blocks, uint8_t* d_base,
+                       uint64_t span_bytes, uint64_t* d_info, void* stream);
 
 /* ---- host write side (inputs for benches and the table facade) ---------------------------
  * SsTableBuilder::add + block_build (src/table/builder.rs:49-85) with BlockBuilder's fill rule

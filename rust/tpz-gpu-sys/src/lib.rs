@@ -64,6 +64,14 @@ pub const TPZ_SCAN_DONE: u8 = 0;
 pub const TPZ_SCAN_MORE: u8 = 1;
 pub const TPZ_SCAN_ERROR: u8 = 2;
 
+/// The header declares `tpz_entries_bound` / `tpz_table_cut` / `tpz_sst_finish` (additive within
+/// ABI 8).
+pub const TPZ_HAS_TABLES: u32 = 1;
+/// `tpz_table_cut`'s `d_cut[0]`.
+pub const TPZ_CUT_NONE: u64 = 0;
+pub const TPZ_CUT_FOUND: u64 = 1;
+pub const TPZ_CUT_BAD_ENTRY: u64 = 2;
+
 /// `tpz_batch`: blocks (or ranges, or files) back to back in HBM; block i is
 /// `d_src[d_ext[i] .. d_ext[i + 1])`.
 #[repr(C)]
@@ -158,6 +166,24 @@ pub struct TpzGetTable {
 /// The header declares this struct with a tag, so the extern block names it as the header does.
 #[allow(non_camel_case_types)]
 pub type tpz_get_table = TpzGetTable;
+
+/// `tpz_sst_image`: one output table of `tpz_sst_finish`; its data region sits at `d_image`
+/// already (`d_filter` null: no bloom section).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct TpzSstImage {
+    pub d_image: *mut u8,
+    pub data_bytes: u64,
+    pub d_first: *const u32,
+    pub d_ext: *const u64,
+    pub n_blocks: u32,
+    pub entry_base: u32,
+    pub d_filter: *const u8,
+    pub filter_len: u64,
+}
+/// Declared with a tag in the header, as `tpz_get_table` is.
+#[allow(non_camel_case_types)]
+pub type tpz_sst_image = TpzSstImage;
 
 /// `tpz_entries`: sorted entries in HBM (the write side).
 #[repr(C)]
@@ -282,6 +308,19 @@ extern "C" {
     pub fn tpz_flat_entry_pos(ctx: *mut TpzCtx, cols: *const TpzFlatColumns, n_blocks: u32,
                               d_kpos: *mut u64, d_vpos: *mut u64, d_info: *mut u32,
                               stream: *mut c_void) -> TpzErr;
+    pub fn tpz_entries_bound(ctx: *mut TpzCtx, entries: *const TpzEntries, d_keys: *const u8,
+                             d_key_pos: *const u64, d_inclusive: *const u8, n_probes: u32,
+                             d_out: *mut u32, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_table_cut(ctx: *mut TpzCtx, entries: *const TpzEntries, start: u32,
+                         win_entries: u32, seg_end: u32, d_first: *mut u32, d_ext: *mut u64,
+                         d_cut_ext: *const u64, d_plan_info: *mut u32, block_size: u32,
+                         capacity: u64, d_cut: *mut u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_sst_image_bytes(data_bytes: u64, n_blocks: u64, first_key_bytes: u64,
+                               filter_len: u64) -> u64;
+    pub fn tpz_sst_finish(ctx: *mut TpzCtx, entries: *const TpzEntries,
+                          d_images: *const tpz_sst_image, n_images: u32, max_blocks: u32,
+                          d_base: *mut u8, span_bytes: u64, d_info: *mut u64,
+                          stream: *mut c_void) -> TpzErr;
     pub fn tpz_build_blocks(h_keys: *const u8, h_kpos: *const u64, h_vals: *const u8,
                             h_vpos: *const u64, n_entries: u64, block_size: u32, h_out: *mut u8,
                             out_cap: u64, h_ext: *mut u64, ext_cap: u64, n_blocks: *mut u64,

@@ -30,6 +30,7 @@ GET_NONE = 0xFFFFFFFF     # d_table / d_block / d_entry of a walk that ended now
 SCAN_MAX_TABLES = 64      # TPZ_SCAN_MAX_TABLES
 BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED, BOUND_AFTER = range(4)   # TPZ_BOUND_*
 SCAN_DONE, SCAN_MORE, SCAN_ERROR = range(3)    # tpz_scan_ranges' d_result (TPZ_SCAN_*)
+CUT_NONE, CUT_FOUND, CUT_BAD_ENTRY = range(3)   # tpz_table_cut's d_cut[0] (TPZ_CUT_*)
 MERGE_MAX_RUNS = 256      # TPZ_MERGE_MAX_RUNS
 MERGE_TILE = 1024         # entries per tile-merge workgroup of tpz_merge_runs (csrc kMergeTile)
 MERGE_LANE_COPY_MAX = 256  # longer keys / values are copied by the whole wave (csrc kLaneCopyMax)
@@ -89,6 +90,13 @@ class Entries(C.Structure):
     _fields_ = [("d_keys", C.c_void_p), ("d_kpos", C.c_void_p), ("d_vals", C.c_void_p),
                 ("d_vpos", C.c_void_p), ("n_entries", C.c_uint32), ("key_bytes", C.c_uint64),
                 ("val_bytes", C.c_uint64)]
+
+
+class SstImage(C.Structure):
+    """tpz_sst_image: one output table of tpz_sst_finish (its data region already at d_image)."""
+    _fields_ = [("d_image", C.c_void_p), ("data_bytes", C.c_uint64), ("d_first", C.c_void_p),
+                ("d_ext", C.c_void_p), ("n_blocks", C.c_uint32), ("entry_base", C.c_uint32),
+                ("d_filter", C.c_void_p), ("filter_len", C.c_uint64)]
 
 
 class HostColumns(C.Structure):
@@ -225,6 +233,21 @@ def lib() -> C.CDLL:
             [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                 C.c_void_p]
         L.tpz_scan_entries.restype = C.c_int
+        if not hasattr(L, "tpz_sst_finish"):      # (additive within ABI 8: an older build lacks it)
+            raise TpzError(f"{LIB_PATH} does not export tpz_sst_finish: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_entries_bound.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.tpz_entries_bound.restype = C.c_int
+        L.tpz_table_cut.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_uint32, C.c_uint32,
+                                    C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.tpz_table_cut.restype = C.c_int
+        L.tpz_sst_image_bytes.argtypes = [C.c_uint64] * 4
+        L.tpz_sst_image_bytes.restype = C.c_uint64
+        L.tpz_sst_finish.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.tpz_sst_finish.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -579,6 +602,33 @@ class Context:
                                      C.c_void_p(d_vals), val_cap, C.c_void_p(d_vpos),
                                      C.c_void_p(stream)), "tpz_scan_entries")
 
+    def entries_bound_ptrs(self, ent: Entries, d_keys: int, d_key_pos: int, d_inclusive: int,
+                           n_probes: int, d_out: int, stream: int = 0) -> None:
+        """tpz_entries_bound: per probe key the number of entries below it (or at it, where its
+        flag is set): sub_compact's seek and key_vaild (level.rs:188-206) over merged entries."""
+        check(lib().tpz_entries_bound(self.handle, C.byref(ent), C.c_void_p(d_keys),
+                                      C.c_void_p(d_key_pos), C.c_void_p(d_inclusive), n_probes,
+                                      C.c_void_p(d_out), C.c_void_p(stream)), "tpz_entries_bound")
+
+    def table_cut_ptrs(self, ent: Entries, start: int, win_entries: int, seg_end: int,
+                       d_first: int, d_ext: int, d_cut_ext: int, d_plan_info: int, block_size: int,
+                       capacity: int, d_cut: int, stream: int = 0) -> None:
+        """tpz_table_cut: reach_capacity's cut (builder.rs:88-94) inside a planned window of the
+        table that starts at entry `start`; d_cut: 8 u64 of device memory."""
+        check(lib().tpz_table_cut(self.handle, C.byref(ent), start, win_entries, seg_end,
+                                  C.c_void_p(d_first), C.c_void_p(d_ext), C.c_void_p(d_cut_ext),
+                                  C.c_void_p(d_plan_info), block_size, capacity,
+                                  C.c_void_p(d_cut), C.c_void_p(stream)), "tpz_table_cut")
+
+    def sst_finish_ptrs(self, ent: Entries, d_images: int, n_images: int, max_blocks: int,
+                        d_base: int, span_bytes: int, d_info: int, stream: int = 0) -> None:
+        """tpz_sst_finish: metas, offsets, bloom section and the CRC trailer of n_images SST file
+        images (builder.rs:97-141, file_object.rs:33-48); d_images: SstImage descriptors in device
+        memory; d_info: 4 u64 per image."""
+        check(lib().tpz_sst_finish(self.handle, C.byref(ent), C.c_void_p(d_images), n_images,
+                                   max_blocks, C.c_void_p(d_base), span_bytes, C.c_void_p(d_info),
+                                   C.c_void_p(stream)), "tpz_sst_finish")
+
     def flat_entry_pos_ptrs(self, cols: dict, n_blocks: int, d_kpos: int, d_vpos: int,
                             d_info: int, stream: int = 0) -> None:
         """tpz_flat_entry_pos: the flat columns' entry positions (cols maps FLAT_FIELDS -> pointer)."""
@@ -617,6 +667,11 @@ def bloom_geometry(n_keys: int, fpp: float):
     ln, k = C.c_uint64(), C.c_uint32()
     rc = lib().tpz_bloom_geometry(n_keys, fpp, C.byref(ln), C.byref(k))
     return None if rc != SUCCESS else (int(ln.value), int(k.value))
+
+
+def sst_image_bytes(data_bytes: int, n_blocks: int, first_key_bytes: int, filter_len: int) -> int:
+    """tpz_sst_image_bytes: the size of an SST file image (filter_len 0: no bloom section)."""
+    return int(lib().tpz_sst_image_bytes(data_bytes, n_blocks, first_key_bytes, filter_len))
 
 
 def xxh3_64(b: bytes) -> int:

@@ -146,6 +146,8 @@ struct tpz_workspace {
   void* d_scan = nullptr;       // tpz_scan_ranges: cursors, their statuses, scan partial sums;
                                 // tpz_scan_entries: the scans' byte bases and partial sums
   size_t scan_cap = 0;
+  void* d_tables = nullptr;     // tpz_sst_finish: key-length partial sums, the CRC's ranges and output
+  size_t tables_cap = 0;
   uint32_t* h_info = nullptr;   // pinned: tpz_plan_blocks' read-back of its 16-byte info
 };
 
@@ -175,6 +177,7 @@ void free_workspace(tpz_workspace& w) {
   if (w.d_merge) (void)hipFree(w.d_merge);
   if (w.d_get) (void)hipFree(w.d_get);
   if (w.d_scan) (void)hipFree(w.d_scan);
+  if (w.d_tables) (void)hipFree(w.d_tables);
   if (w.h_info) (void)hipHostFree(w.h_info);
   w = tpz_workspace{};
 }
@@ -1207,6 +1210,119 @@ tpz_err tpz_pack_ends(tpz_ctx* c, const tpz_batch* b, const tpz_columns* cols,
   tpz::PackLaunch a{b->d_ext, b->n_blocks, cols->d_ends, cols->d_count, cols->d_status,
                     cols->d_spill, cols->d_spill_off, d_first, d_dense, cols->d_entry_first};
   tpz::launch_pack_ends(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+static bool entries_ok(const tpz_entries* en) {
+  return en && en->n_entries != 0xFFFFFFFFu && en->d_kpos && en->d_vpos &&
+         !(((uintptr_t)en->d_kpos | (uintptr_t)en->d_vpos) & 7u) &&
+         (en->d_keys || !en->key_bytes);
+}
+
+tpz_err tpz_entries_bound(tpz_ctx* c, const tpz_entries* en, const uint8_t* d_keys,
+                          const uint64_t* d_key_pos, const uint8_t* d_inclusive,
+                          uint32_t n_probes, uint32_t* d_out, void* stream) {
+  if (!c || !entries_ok(en) || !d_key_pos || !d_inclusive || !d_out) return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_key_pos & 7u) || ((uintptr_t)d_out & 3u)) return TPZ_ERR_INVALID_ARG;
+  if (n_probes == 0) return TPZ_SUCCESS;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::BoundLaunch a{en->d_keys, en->d_kpos, en->key_bytes, en->n_entries, d_keys, d_key_pos,
+                     d_inclusive, n_probes, d_out};
+  tpz::launch_entries_bound(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_table_cut(tpz_ctx* c, const tpz_entries* en, uint32_t start, uint32_t win_entries,
+                      uint32_t seg_end, uint32_t* d_first, uint64_t* d_ext,
+                      const uint64_t* d_cut_ext, uint32_t* d_plan_info, uint32_t block_size,
+                      uint64_t capacity, uint64_t* d_cut, void* stream) {
+  if (!c || !entries_ok(en) || !d_cut || ((uintptr_t)d_cut & 7u)) return TPZ_ERR_INVALID_ARG;
+  if (capacity == 0 || block_size <= 2 || block_size > 65536) return TPZ_ERR_INVALID_ARG;
+  if (seg_end > en->n_entries || start > seg_end || win_entries > seg_end - start)
+    return TPZ_ERR_INVALID_ARG;
+  if (win_entries) {
+    if (!d_first || !d_ext || !d_cut_ext || !d_plan_info) return TPZ_ERR_INVALID_ARG;
+    if ((((uintptr_t)d_ext | (uintptr_t)d_cut_ext) & 7u) ||
+        (((uintptr_t)d_first | (uintptr_t)d_plan_info) & 3u))
+      return TPZ_ERR_INVALID_ARG;
+  }
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::CutLaunch a{en->d_kpos, en->d_vpos, start,       win_entries, seg_end,  d_first,
+                   d_ext,      d_cut_ext,  d_plan_info, block_size,  capacity, d_cut};
+  tpz::launch_table_cut(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+uint64_t tpz_sst_image_bytes(uint64_t data_bytes, uint64_t n_blocks, uint64_t first_key_bytes,
+                             uint64_t filter_len) {
+  // data | metas | meta offset | [filter | bloom offset] | CRC; no filter has length 0 (Bloom::
+  // encode always ends in its k byte)
+  return data_bytes + 6 * n_blocks + first_key_bytes + 4 + (filter_len ? filter_len + 4 : 0) + 4;
+}
+
+tpz_err tpz_sst_finish(tpz_ctx* c, const tpz_entries* en, const tpz_sst_image* d_images,
+                       uint32_t n_images, uint32_t max_blocks, uint8_t* d_base,
+                       uint64_t span_bytes, uint64_t* d_info, void* stream) {
+  if (!c || !entries_ok(en)) return TPZ_ERR_INVALID_ARG;
+  if (n_images == 0) return TPZ_SUCCESS;
+  if (!d_images || !d_base || !d_info || n_images > 65535u || span_bytes > (1ull << 35))
+    return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_images | (uintptr_t)d_info) & 7u) return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t P = tpz::finish_parts(max_blocks);
+  const uint32_t n_ranges = 2 * n_images;
+  // workspace: the partial sums, the CRC's ranges (2 n + 1 u64), its output (2 n u32)
+  const size_t part_words = (size_t)n_images * P;
+  const size_t bytes = (part_words + n_ranges + 1) * 8 + (size_t)n_ranges * 4;
+  uint64_t* work = nullptr;
+  uint32_t* acc = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_tables, &w.tables_cap, bytes);
+    if (r == TPZ_SUCCESS) r = get_acc(c, stream, n_ranges, &acc);
+    if (r != TPZ_SUCCESS) return r;
+    work = static_cast<uint64_t*>(w.d_tables);
+  }
+  tpz::FinishLaunch a{};
+  a.keys = en->d_keys;
+  a.kpos = en->d_kpos;
+  a.key_bytes = en->key_bytes;
+  a.n_entries = en->n_entries;
+  a.images = d_images;
+  a.n_images = n_images;
+  a.max_blocks = max_blocks;
+  a.base = d_base;
+  a.span = span_bytes;
+  a.part = work;
+  a.crc_ext = work + part_words;
+  uint32_t* d_crc = reinterpret_cast<uint32_t*>(a.crc_ext + n_ranges + 1);
+  a.crc = d_crc;
+  a.info = d_info;
+  tpz::launch_finish_layout(a, s);
+  TPZ_HIP(hipGetLastError());
+  // FileObject::create's checksum over every image (and, unused, the bytes between them): the
+  // whole-range CRC with the 4-byte trailer left out
+  TPZ_HIP(hipMemsetAsync(acc, 0, (size_t)n_ranges * 4, s));
+  tpz::CrcLaunch r{};
+  r.src = d_base;
+  r.ext = a.crc_ext;
+  r.src_bytes = span_bytes;
+  r.n_ranges = n_ranges;
+  r.trailer = 4;
+  r.tables = c->d_range_tables;
+  r.rep = c->d_rep_tables;
+  r.acc = acc;
+  r.crc = d_crc;
+  r.status = nullptr;
+  r.num_cus = c->num_cus;
+  tpz::launch_crc_ranges(r, s);
+  TPZ_HIP(hipGetLastError());
+  tpz::launch_finish_crc(a, s);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }

@@ -416,6 +416,56 @@ struct ScanEntriesLaunch {
 uint64_t scan_entries_work_bytes(uint32_t n_scans);
 void launch_scan_entries(const ScanEntriesLaunch& a, hipStream_t stream);
 
+// tpz_entries_bound / tpz_table_cut / tpz_sst_finish (tpz_tables.hip): a compaction task's key
+// ranges, table cuts and SST file images.
+struct BoundLaunch {
+  const uint8_t* keys;
+  const uint64_t* kpos;
+  uint64_t key_bytes;
+  uint32_t n;
+  const uint8_t* q;
+  const uint64_t* q_pos;
+  const uint8_t* incl;
+  uint32_t n_q;                 // > 0
+  uint32_t* out;
+};
+void launch_entries_bound(const BoundLaunch& a, hipStream_t stream);
+struct CutLaunch {
+  const uint64_t* kpos;
+  const uint64_t* vpos;
+  uint32_t start;
+  uint32_t win;
+  uint32_t seg_end;
+  uint32_t* first;
+  uint64_t* ext;
+  const uint64_t* cut_ext;
+  uint32_t* info;
+  uint32_t block_size;
+  uint64_t capacity;
+  uint64_t* cut;                // 8 u64
+};
+void launch_table_cut(const CutLaunch& a, hipStream_t stream);
+struct FinishLaunch {
+  const uint8_t* keys;
+  const uint64_t* kpos;
+  uint64_t key_bytes;
+  uint32_t n_entries;
+  const tpz_sst_image* images;  // device
+  uint32_t n_images;            // 1 .. 65535 (a grid dimension)
+  uint32_t max_blocks;
+  uint8_t* base;
+  uint64_t span;
+  uint64_t* part;               // workspace: n_images x finish_parts(max_blocks) u64
+  uint64_t* crc_ext;            // workspace: 2 n_images + 1 u64 (the CRC's ranges)
+  const uint32_t* crc;          // workspace: 2 n_images u32 (the CRC's output)
+  uint64_t* info;               // 4 u64 per image
+};
+uint32_t finish_parts(uint32_t max_blocks);
+// The metas, offsets and filters of every image and the CRC's ranges; then, after
+// launch_crc_ranges over crc_ext (trailer 4), the images' CRC bytes.
+void launch_finish_layout(const FinishLaunch& a, hipStream_t stream);
+void launch_finish_crc(const FinishLaunch& a, hipStream_t stream);
+
 // tpz_compress_blocks (tpz_compress.hip): scratch bytes for the per-block slots; the snappy
 // encode, the scan of the sizes into dst_ext and the packing into dst.
 uint64_t compress_scratch_bytes(uint64_t src_bytes, uint32_t n_blocks);

@@ -630,6 +630,15 @@ class SsTable:
         """table.rs:178-182: partition_point(first_key <= key) - 1, saturating."""
         return max(bisect.bisect_right([m.first_key for m in self.block_metas], key) - 1, 0)
 
+    def overlap_size(self, lower: bytes, upper: bytes) -> int:
+        """table.rs:127-141: the offset of upper's block minus the offset of lower's (what
+        RwsSlice::create sums per key range, src/level/range.rs:72-81)."""
+        offs = [m.offset for m in self.block_metas]
+        lo, hi = self.find_block_idx(lower), self.find_block_idx(upper)
+        loff = offs[lo] if lo < len(offs) else self.block_meta_offset
+        roff = offs[hi] if hi < len(offs) else self.block_meta_offset
+        return roff - loff
+
     def num_of_blocks(self) -> int:
         return len(self.block_metas)
 
