@@ -30,7 +30,9 @@
 //  non-empty key and value goes into one entry table plus a chunk->entry map. The copy is
 //  output-driven over that single stream: lane c assembles output chunk c from the (usually
 //  one) source segment(s) covering it, then one coalesced dwordx4 store (1 KiB per wave
-//  instruction).
+//  instruction). A regular block (every entry one key length and one value length, both >= 16,
+//  back to back) skips the table and the map on the slotted wave path: its ends and the copy's
+//  chunk -> entry index are closed forms of (n, KL, VL) (decode_block, copy_crc_piped<.., REG>).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1101,11 +1103,41 @@ struct PWin3 {
   Gath g2;
 };
 
-template <bool FLAT, u32 K3>
+// A regular block (decode_block): n entries at db + i S, S = 4 + KL + VL, every key KL and every
+// value VL bytes, both >= 16. Its stream is n keys back to back, then from vs = value_start(n KL)
+// n values back to back, so the entry that holds an output chunk and where its bytes lie follow
+// from the chunk index: no entry table, no chunk map.
+struct RegGeom {
+  u32 n, KL, VL, db;
+};
+// Division of y < 4352 by a wave-uniform d in 16..4336 as (y * m) >> 26. It is exact for every m
+// with 0 <= m d - 2^26 < 2^26 / 4352 = 15420, which holds for floor(2^26 / d) + 1 .. + 3 (3 d <=
+// 13008). v_rcp_f32 is good to 1 ulp, so the truncated 2^26 * rcp(d) <= 2^22 lies within 1 of
+// floor(2^26 / d), and adding 2 lands in that range (tests/test_regular_index.py walks every
+// divisor and dividend). y and m are below 2^24: the product is two 24-bit multiplies.
+constexpr u32 kRegShift = 26;
+__device__ __forceinline__ u32 reg_recip(u32 d) {
+  u32 m = (u32)(__builtin_amdgcn_rcpf((float)d) * (float)(1u << kRegShift)) + 2u;
+  asm volatile("" : "+v"(m));   // (finished here, once per block, not behind the readfirstlane)
+  return uni(m);
+}
+// (the masks tell the compiler that the factors fit 24 bits: full-rate v_mul_u32_u24 /
+// v_mul_hi_u32_u24 instead of the quarter-rate 32-bit multiplies)
+__device__ __forceinline__ u32 mul24(u32 a, u32 b) { return (a & 0xFFFFFFu) * (b & 0xFFFFFFu); }
+__device__ __forceinline__ u32 reg_div(u32 y, u32 m) {
+  const u64 p = (u64)(y & 0x1FFFu) * (u64)(m & 0x7FFFFFu);
+  return __builtin_amdgcn_alignbit((u32)(p >> 32), (u32)p, kRegShift) & 0x3FFu;
+}
+
+// REG: the block is regular (G) and the windows' j, e0, d0, d1, cross come from reg_index instead
+// of the map, the prefix max and the entry table (col, map, nk are not read).
+template <bool FLAT, u32 K3, bool REG = false>
 __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& col,
                                               const uint16_t* map, u32 nk, u32 tot, uint8_t* dst,
                                               const FlatOut& D, const uint8_t* win, int pb, u32 Pa,
-                                              const Out& o, PendingCrc& pd, u32 k3n = K3) {
+                                              const Out& o, PendingCrc& pd, u32 k3n = K3,
+                                              const RegGeom G = RegGeom{0u, 0u, 0u, 0u}) {
+  static_assert(!REG || (K3 == 0 && !FLAT), "the regular copy: slotted, no short keys");
   // (k3n <= K3, uniform: the windows that hold short keys; the others take the plain rule)
   const u32 lane = lane_id();
   FastWin F;
@@ -1126,12 +1158,42 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   };
   PWin W[4];
   PWin3 W3;
+  // REG: chunk c at x0 = 16 c lies in key j = x0 / KL (x0 < n KL: the values start on a chunk
+  // boundary, so no chunk holds both) or in value j = (x0 - vs) / VL. With L that entry's length,
+  // base the region's start in the stream (0 or vs) and r = x0 - base - j L the chunk's first
+  // byte within the entry, the source is db + j S + 2 (+ 2 + KL) + r, so d0 = source - x0 =
+  // C + j T with T = S - L and C uniform; the entry ends at e0 = base + (j + 1) L, and the next
+  // one's bytes lie T further on (d1 = d0 + T). A chunk crosses at most one boundary (L >= 16).
+  // The last key's chunk crosses into the key/value gap (unspecified bytes): it takes what the
+  // general path reads there, the bytes before value 0 (r_gap: where those lie from the chunk's
+  // own source). The last value has no successor (e0 out of reach).
+  const u32 r_kc = G.n * G.KL, r_vs = (r_kc + 15) & ~15u, r_S = 4 + G.KL + G.VL;
+  const u32 r_mk = REG ? reg_recip(G.KL) : 0u, r_mv = REG ? reg_recip(G.VL) : 0u;
+  const int r_gap = (int)(2 + G.KL) - (int)r_vs - (int)((G.n - 1) * (4 + G.VL));
+  auto reg_entry = [&](PWin& P, u32 x0, bool isk) {
+    const u32 L = isk ? G.KL : G.VL, base = isk ? 0u : r_vs, T = r_S - L;
+    const u32 j = reg_div(x0 - base, isk ? r_mk : r_mv);
+    const bool last = j + 1 == G.n;
+    P.j = 0;
+    P.e0 = (!isk && last) ? 0xFFFFu : base + mul24(j + 1, L);     // (j < 2^10, L and T < 2^13)
+    P.d0 = (int)((isk ? G.db + 2 : G.db + 4 + G.KL - r_vs) + mul24(j, T));
+    P.d1 = P.d0 + ((isk && last) ? r_gap : (int)T);
+  };
+  auto reg_index = [&](PWin& P, u32 w) {
+    const u32 x0 = 16 * (64 * w + lane);
+    // (a window wholly in the keys or wholly in the values: scalar selects)
+    if (1024 * (w + 1) <= r_kc) reg_entry(P, x0, true);
+    else if (1024 * w >= r_vs) reg_entry(P, x0, false);
+    else reg_entry(P, x0, x0 < r_kc);
+    // (computed here, in stage B, not sunk between a window's store and the next one's gathers)
+    asm volatile("" : "+v"(P.e0), "+v"(P.d0), "+v"(P.d1));
+  };
   // A: map reads, CRC data of step 0
 #pragma unroll
   for (int w = 0; w < 4; w++) {
     const u32 c = 64 * w + lane;
     W[w].act = c < F.nch;
-    W[w].m = map[min(c, (u32)kWaveMapLen - 1)];
+    if (!REG) W[w].m = map[min(c, (u32)kWaveMapLen - 1)];
   }
   u32x4v dA = dread(0);
   // the pending combine: level 0, and shift_k(~stored), the value R is compared with
@@ -1140,17 +1202,23 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   const u32 want = crc_shift_small(tab, ~pd.stored, pd.k);
   TPZ_SB();
   // B: prefix max per window (independent DPP chains), carries, entries j and j + 1
-#pragma unroll
-  for (int w = 0; w < 4; w++) W[w].j = wave_scan_max(W[w].act ? W[w].m : 0u);
+  //    (REG: the closed form, no LDS read)
   u32 cw[5];
   cw[0] = 0;
+  if (REG) {
 #pragma unroll
-  for (int w = 0; w < 4; w++) {
-    W[w].j = max(W[w].j, cw[w]);
-    cw[w + 1] = readlane(W[w].j, 63);
+    for (int w = 0; w < 4; w++) reg_index(W[w], (u32)w);
+  } else {
+#pragma unroll
+    for (int w = 0; w < 4; w++) W[w].j = wave_scan_max(W[w].act ? W[w].m : 0u);
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      W[w].j = max(W[w].j, cw[w]);
+      cw[w + 1] = readlane(W[w].j, 63);
+    }
+#pragma unroll
+    for (int w = 0; w < 4; w++) col.get2(min(W[w].j, F.last), W[w].e0, W[w].d0, W[w].e1, W[w].d1);
   }
-#pragma unroll
-  for (int w = 0; w < 4; w++) col.get2(min(W[w].j, F.last), W[w].e0, W[w].d0, W[w].e1, W[w].d1);
   if (K3) col.get2(min(W[0].j + 2, F.last), W3.e2, W3.d2, W3.e3, W3.d3);
   cA = comb_use<0>(cA, cl);
   cl = comb_issue<1>(tab, cA);
@@ -1245,9 +1313,16 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   TPZ_SB();
   crc = look_xor(LK);
   if (nw > 4) {
-    (void)copy_fast<FLAT>(Src16{win}, col, map, F, D, 4u, cw[4], rare);
+    if (REG) {              // the fifth window by the same closed form
+      W[0].act = 256 + lane < F.nch;
+      reg_index(W[0], 4u);
+      gissue(W[0], 4u);
+      finish(W[0], 4u);
+    } else {
+      (void)copy_fast<FLAT>(Src16{win}, col, map, F, D, 4u, cw[4], rare);
+    }
   }
-  if (rare) {
+  if (!REG && rare) {
     for (u32 w = 0; w < nw; w++)
       if (rare & (1u << w)) {
         if (FLAT)
@@ -1259,6 +1334,19 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   return crc;
 }
 
+
+// The window made ready for the CRC of its P >= 4 payload bytes at a0 (after the parse: it
+// changes payload bytes); returns k, the zero bytes from the payload end to the 16-byte boundary.
+__device__ __forceinline__ u32 crc_prepare(uint8_t* win, u32 a0, u32 P) {
+  const u32 lane = lane_id();
+  const u32 k = ((a0 + P + 15) & ~15u) - (a0 + P);
+  if (lane < 4) win[a0 + lane] ^= 0xFFu;
+  // the k bytes to the 16-byte boundary for the CRC; 16 in all, so that the copy's last chunk,
+  // which may read up to 15 bytes past the payload, reads zeros there (deterministic output)
+  if (lane < 16) win[a0 + P + lane] = 0;
+  __builtin_amdgcn_wave_barrier();
+  return k;
+}
 
 // Decode the block whose bytes are at win[a0 .. a0+len) (LDS), block index b. `map` is the
 // stream's chunk map (kMapLen slots, LDS), `col` its entry table.
@@ -1332,6 +1420,54 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
     uint2* ends_g = reinterpret_cast<uint2*>(o.ends) + uni64((FLAT || o.efirst) ? ef : entry_base(ext_b, b));
     // whole 128-byte lines of {kend, vend} in the slotted layout; exactly n in the exact one
     const u32 n_pad = o.efirst ? n : (n + 15) & ~15u;
+    // Round 0's value lengths (slotted wave path), read before the map is cleared: the
+    // regularity test needs them, and the general parse below takes them from here.
+    u32 r_vl = 0;
+    bool r_ok = false;
+    if constexpr (!BIG && !FLAT) {
+      r_ok = e_ok && e_off + 4 + e_kl <= dl;                                     // iterator.rs:77-81
+      if (r_ok) { r_vl = lds_be16(win, db + e_off + 2 + e_kl); r_ok = e_off + 4 + e_kl + r_vl <= dl; }
+      // A regular block: every entry KL key and VL value bytes (entry 0's), both >= 16, at
+      // offset i es, es = 4 + KL + VL, and the reference's bounds checks pass. Then the ends, the
+      // totals and the copy's chunk -> entry rule are closed forms of (n, KL, VL): no map clear,
+      // no scans, no entry table, no map (copy_crc_piped<.., REG>). Anything else (a length that
+      // differs or is under 16, a hole, permuted or repeated offsets, a bad entry) takes the
+      // general parse below; slack after the last entry is allowed.
+      const u32 KL = readlane(e_kl, 0), VL = readlane(r_vl, 0), es = 4 + KL + VL;
+      bool reg = n != 0 && KL >= 16 && VL >= 16 && P >= 4 && slots_fit &&
+                 !__ballot(lane < n && !(r_ok && e_off == mul24(lane, es) && e_kl == KL && r_vl == VL));
+      for (u32 g0 = 64; reg && g0 < n; g0 += 64) {
+        const u32 i = g0 + lane;
+        bool same = true;
+        if (i < n) {
+          const u32 off = lds_be16(win, a0 + 2 + 2 * i);
+          same = off == mul24(i, es) && off + 4 + KL + VL <= dl;
+          if (same) same = lds_be16(win, db + off) == KL && lds_be16(win, db + off + 2 + KL) == VL;
+        }
+        reg = !__ballot(!same);
+      }
+      const u32 kc = n * KL, vc = n * VL, vs = stream_vstart<false>(kc, 0u, 0u);
+      if (reg && vs + vc <= len + 2u) {
+        for (u32 g0 = 0; g0 < n; g0 += 64) {
+          const u32 i = g0 + lane;
+          __builtin_amdgcn_raw_buffer_store_b64(
+              __builtin_bit_cast(__attribute__((ext_vector_type(2))) u32,
+                                 i < n ? make_uint2(mul24(i + 1, KL), mul24(i + 1, VL)) : make_uint2(0, 0)),
+              whole_rsrc(ends_g), i < n_pad ? 8 * i : kOob, 0, 0);
+        }
+        TPZ_STAMP(S, 2);
+        TPZ_STAMP(S, 3);
+        __builtin_amdgcn_wave_barrier();
+        const u32 k = crc_prepare(win, a0, P);
+        fin.on = false;     // the previous block's combine runs in the copy, before pd is reused
+        const u32 lc = copy_crc_piped<false, 0u, true>(
+            tab, *reinterpret_cast<const ColSmall*>(&col), reinterpret_cast<const uint16_t*>(map),
+            2 * n, vs + vc, o.data + slot_base(ext_b, b), fo, win, pb, P + k, o, pd, 0u,
+            RegGeom{n, KL, VL, db});
+        pd = PendingCrc{1u, b, st, cnt, stored, k, lc, 0u};   // combined during the next block
+        return;
+      }
+    }
     {
       // clear the chunk map up to the largest chunk index a block that fits its slot can
       // produce (stream <= len + 2 bytes; the others go to the spill path)
@@ -1367,16 +1503,23 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
       u32 off = 0, kl = 0, vl = 0;
       bool ok = true;
       if (act) {
-        if (!BIG && g0 == 0) {          // (read before the combine: e_ok = act && off + 2 <= dl)
+        if (!BIG && !FLAT && g0 == 0) { // (read for the regularity test above)
           off = e_off;
-          ok = e_ok;
-          if (ok) { kl = e_kl; ok = off + 4 + kl <= dl; }
+          kl = e_kl;
+          vl = r_vl;
+          ok = r_ok;
         } else {
-          off = lds_be16(win, a0 + 2 + 2 * i);                                    // iterator.rs:74
-          ok = off + 2 <= dl;
-          if (ok) { kl = lds_be16(win, db + off); ok = off + 4 + kl <= dl; }      // :77-81
+          if (!BIG && g0 == 0) {        // (read before the combine: e_ok = act && off + 2 <= dl)
+            off = e_off;
+            ok = e_ok;
+            if (ok) { kl = e_kl; ok = off + 4 + kl <= dl; }
+          } else {
+            off = lds_be16(win, a0 + 2 + 2 * i);                                  // iterator.rs:74
+            ok = off + 2 <= dl;
+            if (ok) { kl = lds_be16(win, db + off); ok = off + 4 + kl <= dl; }    // :77-81
+          }
+          if (ok) { vl = lds_be16(win, db + off + 2 + kl); ok = off + 4 + kl + vl <= dl; } // :81-82
         }
-        if (ok) { vl = lds_be16(win, db + off + 2 + kl); ok = off + 4 + kl + vl <= dl; } // :81-82
         if (!ok) kl = vl = 0;
       }
       bad |= __ballot(act && !ok) != 0;
@@ -1473,12 +1616,7 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
     // end to the next 16-byte boundary (stored CRC and tag are already in registers). Then
     // R = R0(payload' || 0^k) = shift_k(R0(payload')), which equals shift_k(~stored) iff the CRC
     // matches. (The window is not used after this, so nothing is restored.)
-    const u32 k = ((a0 + P + 15) & ~15u) - (a0 + P);
-    if (lane < 4) win[a0 + lane] ^= 0xFFu;
-    // the k bytes to the 16-byte boundary for the CRC; 16 in all, so that the copy's last chunk,
-    // which may read up to 15 bytes past the payload, reads zeros there (deterministic output)
-    if (lane < 16) win[a0 + P + lane] = 0;
-    __builtin_amdgcn_wave_barrier();
+    const u32 k = crc_prepare(win, a0, P);
 #if defined(TPZ_ABL_NOCRC) || defined(TPZ_ABL_MEMONLY)
     crc = stored;
 #else
