@@ -76,7 +76,11 @@ extern "C" {
  *      tpz_scan_entries (LsmStorage::scan's SST half), TPZ_BOUND_*, TPZ_SCAN_*; a consumer tests
  *      TPZ_HAS_SCAN. Same ABI, additive: tpz_entries_bound, tpz_table_cut, tpz_sst_finish and
  *      tpz_sst_image_bytes (a compaction task's key ranges, table cuts and SST file images),
- *      tpz_sst_image, TPZ_CUT_*; a consumer tests TPZ_HAS_TABLES
+ *      tpz_sst_image, TPZ_CUT_*; a consumer tests TPZ_HAS_TABLES. Same ABI, additive: memtable
+ *      runs as a resident input (tpz_mem_run, tpz_mem_prefix, TPZ_MEM_MAX_RUNS, TPZ_HIT_MEM) and
+ *      LsmStorage::get and LsmStorage::scan over runs plus tables (tpz_lsm_get_keys,
+ *      tpz_lsm_get_values, tpz_lsm_scan_ranges, tpz_lsm_scan_entries); a consumer tests
+ *      TPZ_HAS_MEM
  * A consumer compiled against one header checks tpz_abi_version() == TPZ_ABI_VERSION. */
 #define TPZ_ABI_VERSION 8
 int tpz_abi_version(void);
@@ -770,7 +774,8 @@ tpz_err tpz_get_values(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n_t
  *      in increasing priority, until its key differs, then the current cursor once. An Err from
  *      any of these steps ends the scan.
  *   4. TwoMergeIterator with an always-invalid memtable side passes that sequence e0, e1, ..
- *      through; the host merges its memtables over the device's output.
+ *      through; the host merges its memtables over the device's output, or hands them over as
+ *      runs (tpz_lsm_scan_ranges, below: the real TwoMergeIterator).
  *   5. LsmIterator (src/lsm_iterator.rs): entries with an empty value are skipped; every element
  *      AFTER e0, tombstones included, is tested against the end bound (Included stops at the
  *      first key > upper, Excluded at the first key >= upper) and the first failure ends the scan.
@@ -847,6 +852,121 @@ tpz_err tpz_scan_entries(tpz_ctx* ctx, const tpz_get_table* d_tables, uint32_t n
                          const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
                          uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
                          void* stream);
+
+/* ---- memtable runs: LsmStorage::get and LsmStorage::scan over runs plus tables -------------
+ * What a user of the store calls: LsmStorage::get (src/lsm_storage.rs:198-213) looks in the
+ * memtables first, newest first, and only then in the tables (LevelController::get, above);
+ * LsmStorage::scan (:335-374) merges the memtables in with TwoMergeIterator. Additive within
+ * ABI 8: new symbols and constants only (TPZ_HAS_MEM tells a consumer the header has them).
+ *
+ * A run is one memtable's SkipMap (src/mem_table.rs) as a tpz_entries in DEVICE memory: its keys
+ * strictly increasing (a map; Rust's [u8] Ord), a tombstone an entry with an empty value.
+ * d_prefix is NULL or n_entries u64: entry j's key's first 8 bytes, big-endian, zero padded, which
+ * tpz_mem_prefix builds (asynchronous on `stream`; n_entries == 0 does nothing). It is the index
+ * of a lookup: a bisection step over it is one 8-byte load, and key bytes are read only among
+ * entries whose prefix ties with the probe's. A tie decides nothing (`a` and `a\0` share a
+ * prefix, long keys share 8-byte prefixes): the full comparison follows. With d_prefix NULL the
+ * same bisection reads the keys; both forms give identical answers.
+ * d_runs: n_runs descriptors in DEVICE memory, in MemTables::view() order (src/mem_table.rs:74-81):
+ * the immutable memtables oldest first, the mutable one last. Priority is the reverse.
+ * Unsorted or repeated keys in a run, or a d_prefix that is not the keys' prefix column, are a
+ * precondition violation: the results are then unspecified, but every loop is bounded, every
+ * index clamped, and nothing is written outside the stated capacities.
+ *
+ * tpz_lsm_get_keys: tpz_get_keys' arguments with d_runs, n_runs in front, and its output
+ * columns. Per query:
+ *   - an empty key: LsmStorage::get asserts (:199). TPZ_GET_ERROR with TPZ_BLOCK_MALFORMED and
+ *     d_table = d_block = d_entry = 0xFFFFFFFF (tpz_get_keys keeps accepting empty keys);
+ *   - the runs from n_runs - 1 down to 0 with an exact match (MemTable::get, src/mem_table.rs:
+ *     150-152). The first run holding the key ends the get (:202-209): an empty value is
+ *     TPZ_GET_DELETED, any other TPZ_GET_FOUND, with d_table = TPZ_HIT_MEM | run, d_block = 0,
+ *     d_entry = the index in the run, and the value length in d_val_pos as for a table hit;
+ *   - no run holds it: tpz_get_keys' walk, unchanged (:211).
+ * tpz_lsm_get_values is tpz_get_values over both sources in one pass: run and entry are checked
+ * against the run descriptors as table, block and entry are against the tables', and nothing is
+ * written at or past val_cap.
+ * With n_runs == 0 both give tpz_get_keys' / tpz_get_values' outputs byte for byte for non-empty
+ * keys. TPZ_ERR_INVALID_ARG, before any device work, for n_runs > TPZ_MEM_MAX_RUNS, a null or
+ * misaligned d_runs with n_runs > 0, and everything tpz_get_keys / tpz_get_values reject.
+ *
+ * tpz_lsm_scan_ranges / tpz_lsm_scan_entries: tpz_scan_ranges' / tpz_scan_entries' arguments with
+ * d_runs, n_runs in front, and their outputs: LsmStorage::scan whole. Step 4 of the scan section
+ * above becomes the real TwoMergeIterator (src/iterators/two_merge_iterator.rs), A = the
+ * MergeIterator over one cursor per memtable, newest first (lsm_storage.rs:340-346), B = the SST
+ * MergeIterator of steps 1-3. One wave still merges a scan, a cursor per lane: the runs newest
+ * first, then the tables in level_tables_sorted order; n_runs + n_tables > TPZ_SCAN_MAX_TABLES is
+ * TPZ_ERR_INVALID_ARG.
+ *   - A run's cursor is map.range((lower, upper)) (src/mem_table.rs:199-219): unlike an SST
+ *     cursor it is bounded on both sides. It covers the run's entries [lb, ub): lb = 0 for
+ *     Unbounded, the number of keys < lower for Included, of keys <= lower for Excluded and
+ *     After; ub = n_entries for Unbounded, the number of keys <= upper for Included, of keys
+ *     < upper for Excluded. With lower > upper, or equal keys and an Excluded side, the cursor is
+ *     empty. (BTreeMap::range panics on such bounds; this header takes crossbeam-skiplist's range
+ *     to yield nothing there, which is a decision: its source was not at hand.) Run cursors
+ *     never fail.
+ *   - The cursor is valid iff lb < ub and the key at lb is non-empty (MemTableIterator::is_valid,
+ *     :263-265). batch_put and the channel writers do not assert on keys, so a run can hold the
+ *     empty key as its first entry; a cursor that starts on it is invalid, MergeIterator::create
+ *     drops it, and that memtable contributes nothing to the scan. The device reproduces this.
+ *   - The yielded sequence is what one flat merge over all lanes in that priority order yields:
+ *     TwoMergeIterator prefers A on a tie and skips B's equal keys. Where the work happens
+ *     differs, and errors show it: create() and every next() step B past every key equal to A's
+ *     current key BEFORE that key is yielded (two_merge_iterator.rs:20-24, :64-68), with B's own
+ *     "others first" order. An Err from a block read during that skip therefore ends the scan one
+ *     element earlier than a flat merge would report it; if the skip happens in create(), or in
+ *     LsmIterator::new's tombstone skip, scan() itself returns the Err and the count is 0.
+ *     d_first on ERROR stays "entries the reference's iterator yielded before the failing step",
+ *     and d_where is the failing SST cursor in MergeIterator::next's order.
+ *   - LsmIterator is unchanged (step 5): e0 is never end-checked unless the lower kind is After;
+ *     because run cursors are bounded above, that quirk can only fire from an SST lane.
+ *     TPZ_BOUND_AFTER applies Excluded to run cursors too. TPZ_SCAN_MORE keeps its meaning (an
+ *     Err in the step after the last yielded entry is ERROR with count `limit`), and pages
+ *     concatenate to the unpaged scan when every block is readable and the runs are the same
+ *     snapshot.
+ * A yielded run entry reports d_hit_table = TPZ_HIT_MEM | run, d_hit_block = 0, d_hit_entry = its
+ * index; tpz_lsm_scan_entries gathers from both kinds with tpz_scan_entries' checks (run and
+ * entry against the run descriptors). With n_runs == 0 both reproduce tpz_scan_ranges /
+ * tpz_scan_entries byte for byte. The workspace holds a cursor per scan and run too. */
+#define TPZ_HAS_MEM 1
+#define TPZ_MEM_MAX_RUNS 16u    /* the reference's default max_memtable_num is 5 (src/opt.rs:41) */
+#define TPZ_HIT_MEM 0x80000000u /* d_table = TPZ_HIT_MEM | run for a hit in a memtable run */
+/* (declared with a tag, as tpz_get_table is) */
+struct tpz_mem_run {
+  tpz_entries entries;
+  const uint64_t* d_prefix; /* n_entries u64, or NULL */
+};
+typedef struct tpz_mem_run tpz_mem_run;
+
+tpz_err tpz_mem_prefix(tpz_ctx* ctx, const tpz_entries* entries, uint64_t* d_prefix, void* stream);
+tpz_err tpz_lsm_get_keys(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                         const tpz_get_table* d_tables, uint32_t n_tables,
+                         const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                         const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                         uint8_t* d_status, uint32_t* d_table, uint32_t* d_block,
+                         uint32_t* d_entry, uint64_t* d_val_pos, void* stream);
+tpz_err tpz_lsm_get_values(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                           const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_keys,
+                           const uint8_t* d_result, const uint32_t* d_table,
+                           const uint32_t* d_block, const uint32_t* d_entry,
+                           const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
+                           void* stream);
+tpz_err tpz_lsm_scan_ranges(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                            const tpz_get_table* d_tables, uint32_t n_tables,
+                            const uint32_t* h_level_first, uint32_t n_levels,
+                            const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                            const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                            const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans,
+                            uint32_t limit, uint8_t* d_result, uint8_t* d_status,
+                            uint32_t* d_where, uint32_t* d_hit_table, uint32_t* d_hit_block,
+                            uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
+                            uint64_t* d_val_first, uint64_t* d_info, void* stream);
+tpz_err tpz_lsm_scan_entries(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                             const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_scans,
+                             uint32_t limit, const uint32_t* d_hit_table,
+                             const uint32_t* d_hit_block, const uint32_t* d_hit_entry,
+                             const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
+                             uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
+                             void* stream);
 
 /* ---- a whole compaction task's output tables ----------------------------------------------
  * What do_compact (src/level.rs:133-222) does around the merge and the block loop: the key ranges

@@ -72,6 +72,14 @@ pub const TPZ_CUT_NONE: u64 = 0;
 pub const TPZ_CUT_FOUND: u64 = 1;
 pub const TPZ_CUT_BAD_ENTRY: u64 = 2;
 
+/// The header declares `tpz_mem_prefix`, `tpz_lsm_get_keys` / `tpz_lsm_get_values` and
+/// `tpz_lsm_scan_ranges` / `tpz_lsm_scan_entries` (additive within ABI 8).
+pub const TPZ_HAS_MEM: u32 = 1;
+/// The most memtable runs one call takes.
+pub const TPZ_MEM_MAX_RUNS: u32 = 16;
+/// `d_table = TPZ_HIT_MEM | run` for a hit in a memtable run.
+pub const TPZ_HIT_MEM: u32 = 0x80000000;
+
 /// `tpz_batch`: blocks (or ranges, or files) back to back in HBM; block i is
 /// `d_src[d_ext[i] .. d_ext[i + 1])`.
 #[repr(C)]
@@ -198,6 +206,18 @@ pub struct TpzEntries {
     pub val_bytes: u64,
 }
 
+/// `tpz_mem_run`: one memtable's sorted snapshot in HBM (`MemTables::view()` order in `d_runs`:
+/// immutable memtables oldest first, the mutable one last); `d_prefix` null: no prefix column.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct TpzMemRun {
+    pub entries: TpzEntries,
+    pub d_prefix: *const u64,
+}
+/// Declared with a tag in the header, as `tpz_get_table` is.
+#[allow(non_camel_case_types)]
+pub type tpz_mem_run = TpzMemRun;
+
 /// `tpz_ctx` (opaque).
 #[repr(C)]
 pub struct TpzCtx {
@@ -291,6 +311,36 @@ extern "C" {
                           n_keys: u32, d_result: *const u8, d_table: *const u32,
                           d_block: *const u32, d_entry: *const u32, d_val_pos: *const u64,
                           d_vals: *mut u8, val_cap: u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_mem_prefix(ctx: *mut TpzCtx, entries: *const TpzEntries, d_prefix: *mut u64,
+                          stream: *mut c_void) -> TpzErr;
+    pub fn tpz_lsm_get_keys(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                            d_tables: *const tpz_get_table, n_tables: u32,
+                            h_level_first: *const u32, n_levels: u32, d_keys: *const u8,
+                            d_key_pos: *const u64, n_keys: u32, d_result: *mut u8,
+                            d_status: *mut u8, d_table: *mut u32, d_block: *mut u32,
+                            d_entry: *mut u32, d_val_pos: *mut u64,
+                            stream: *mut c_void) -> TpzErr;
+    pub fn tpz_lsm_get_values(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                              d_tables: *const tpz_get_table, n_tables: u32, n_keys: u32,
+                              d_result: *const u8, d_table: *const u32, d_block: *const u32,
+                              d_entry: *const u32, d_val_pos: *const u64, d_vals: *mut u8,
+                              val_cap: u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_lsm_scan_ranges(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                               d_tables: *const tpz_get_table, n_tables: u32,
+                               h_level_first: *const u32, n_levels: u32, d_lo_keys: *const u8,
+                               d_lo_pos: *const u64, d_lo_kind: *const u8, d_hi_keys: *const u8,
+                               d_hi_pos: *const u64, d_hi_kind: *const u8, n_scans: u32,
+                               limit: u32, d_result: *mut u8, d_status: *mut u8,
+                               d_where: *mut u32, d_hit_table: *mut u32, d_hit_block: *mut u32,
+                               d_hit_entry: *mut u32, d_first: *mut u64, d_key_first: *mut u64,
+                               d_val_first: *mut u64, d_info: *mut u64,
+                               stream: *mut c_void) -> TpzErr;
+    pub fn tpz_lsm_scan_entries(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                                d_tables: *const tpz_get_table, n_tables: u32, n_scans: u32,
+                                limit: u32, d_hit_table: *const u32, d_hit_block: *const u32,
+                                d_hit_entry: *const u32, d_first: *const u64, d_keys: *mut u8,
+                                key_cap: u64, d_kpos: *mut u64, d_vals: *mut u8, val_cap: u64,
+                                d_vpos: *mut u64, stream: *mut c_void) -> TpzErr;
     pub fn tpz_scan_ranges(ctx: *mut TpzCtx, d_tables: *const tpz_get_table, n_tables: u32,
                            h_level_first: *const u32, n_levels: u32, d_lo_keys: *const u8,
                            d_lo_pos: *const u64, d_lo_kind: *const u8, d_hi_keys: *const u8,

@@ -28,6 +28,8 @@ GET_MAX_LEVELS = 16       # TPZ_GET_MAX_LEVELS
 GET_ABSENT, GET_FOUND, GET_DELETED, GET_ERROR = range(4)   # tpz_get_keys' d_result (TPZ_GET_*)
 GET_NONE = 0xFFFFFFFF     # d_table / d_block / d_entry of a walk that ended nowhere
 SCAN_MAX_TABLES = 64      # TPZ_SCAN_MAX_TABLES
+MEM_MAX_RUNS = 16         # TPZ_MEM_MAX_RUNS
+HIT_MEM = 0x80000000      # TPZ_HIT_MEM: d_table = HIT_MEM | run for a hit in a memtable run
 BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED, BOUND_AFTER = range(4)   # TPZ_BOUND_*
 SCAN_DONE, SCAN_MORE, SCAN_ERROR = range(3)    # tpz_scan_ranges' d_result (TPZ_SCAN_*)
 CUT_NONE, CUT_FOUND, CUT_BAD_ENTRY = range(3)   # tpz_table_cut's d_cut[0] (TPZ_CUT_*)
@@ -90,6 +92,11 @@ class Entries(C.Structure):
     _fields_ = [("d_keys", C.c_void_p), ("d_kpos", C.c_void_p), ("d_vals", C.c_void_p),
                 ("d_vpos", C.c_void_p), ("n_entries", C.c_uint32), ("key_bytes", C.c_uint64),
                 ("val_bytes", C.c_uint64)]
+
+
+class MemRun(C.Structure):
+    """tpz_mem_run: one memtable's sorted snapshot in HBM (d_prefix None: no prefix column)."""
+    _fields_ = [("entries", Entries), ("d_prefix", C.c_void_p)]
 
 
 class SstImage(C.Structure):
@@ -248,6 +255,23 @@ def lib() -> C.CDLL:
         L.tpz_sst_finish.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_void_p, C.c_uint32,
                                      C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.tpz_sst_finish.restype = C.c_int
+        if not hasattr(L, "tpz_lsm_get_keys"):    # (additive within ABI 8: an older build lacks it)
+            raise TpzError(f"{LIB_PATH} does not export tpz_lsm_get_keys: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_mem_prefix.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_void_p, C.c_void_p]
+        L.tpz_mem_prefix.restype = C.c_int
+        L.tpz_lsm_get_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + \
+            list(L.tpz_get_keys.argtypes[1:])
+        L.tpz_lsm_get_keys.restype = C.c_int
+        L.tpz_lsm_get_values.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + \
+            list(L.tpz_get_values.argtypes[1:])
+        L.tpz_lsm_get_values.restype = C.c_int
+        L.tpz_lsm_scan_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + \
+            list(L.tpz_scan_ranges.argtypes[1:])
+        L.tpz_lsm_scan_ranges.restype = C.c_int
+        L.tpz_lsm_scan_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + \
+            list(L.tpz_scan_entries.argtypes[1:])
+        L.tpz_lsm_scan_entries.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -571,6 +595,69 @@ class Context:
                                    C.c_void_p(d_result), C.c_void_p(d_table), C.c_void_p(d_block),
                                    C.c_void_p(d_entry), C.c_void_p(d_val_pos), C.c_void_p(d_vals),
                                    val_cap, C.c_void_p(stream)), "tpz_get_values")
+
+    def mem_prefix_ptrs(self, ent: Entries, d_prefix: int, stream: int = 0) -> None:
+        """tpz_mem_prefix: the prefix column of a memtable run (n_entries u64 at d_prefix)."""
+        check(lib().tpz_mem_prefix(self.handle, C.byref(ent), C.c_void_p(d_prefix),
+                                   C.c_void_p(stream)), "tpz_mem_prefix")
+
+    def lsm_get_keys_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                          h_level_first: int, n_levels: int, d_keys: int, d_key_pos: int,
+                          n_keys: int, d_result: int, d_status: int, d_table: int, d_block: int,
+                          d_entry: int, d_val_pos: int, stream: int = 0) -> None:
+        """tpz_lsm_get_keys: LsmStorage::get (lsm_storage.rs:198-213) for every key: the n_runs
+        tpz_mem_run descriptors at d_runs newest first, then tpz_get_keys' walk."""
+        check(lib().tpz_lsm_get_keys(self.handle, C.c_void_p(d_runs), n_runs, C.c_void_p(d_tables),
+                                     n_tables, C.c_void_p(h_level_first), n_levels,
+                                     C.c_void_p(d_keys), C.c_void_p(d_key_pos), n_keys,
+                                     C.c_void_p(d_result), C.c_void_p(d_status),
+                                     C.c_void_p(d_table), C.c_void_p(d_block), C.c_void_p(d_entry),
+                                     C.c_void_p(d_val_pos), C.c_void_p(stream)),
+              "tpz_lsm_get_keys")
+
+    def lsm_get_values_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                            n_keys: int, d_result: int, d_table: int, d_block: int, d_entry: int,
+                            d_val_pos: int, d_vals: int, val_cap: int, stream: int = 0) -> None:
+        """tpz_lsm_get_values: the values of tpz_lsm_get_keys' FOUND queries, from runs and
+        tables, packed at d_val_pos."""
+        check(lib().tpz_lsm_get_values(self.handle, C.c_void_p(d_runs), n_runs,
+                                       C.c_void_p(d_tables), n_tables, n_keys,
+                                       C.c_void_p(d_result), C.c_void_p(d_table),
+                                       C.c_void_p(d_block), C.c_void_p(d_entry),
+                                       C.c_void_p(d_val_pos), C.c_void_p(d_vals), val_cap,
+                                       C.c_void_p(stream)), "tpz_lsm_get_values")
+
+    def lsm_scan_ranges_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                             h_level_first: int, n_levels: int, d_lo_keys: int, d_lo_pos: int,
+                             d_lo_kind: int, d_hi_keys: int, d_hi_pos: int, d_hi_kind: int,
+                             n_scans: int, limit: int, d_result: int, d_status: int, d_where: int,
+                             d_hit_table: int, d_hit_block: int, d_hit_entry: int, d_first: int,
+                             d_key_first: int, d_val_first: int, d_info: int,
+                             stream: int = 0) -> None:
+        """tpz_lsm_scan_ranges: LsmStorage::scan whole (lsm_storage.rs:335-374) for every range:
+        the n_runs tpz_mem_run descriptors at d_runs merged over the tables (TwoMergeIterator)."""
+        ptrs = [C.c_void_p(x) for x in (d_result, d_status, d_where, d_hit_table, d_hit_block,
+                                        d_hit_entry, d_first, d_key_first, d_val_first, d_info)]
+        check(lib().tpz_lsm_scan_ranges(self.handle, C.c_void_p(d_runs), n_runs,
+                                        C.c_void_p(d_tables), n_tables, C.c_void_p(h_level_first),
+                                        n_levels, C.c_void_p(d_lo_keys), C.c_void_p(d_lo_pos),
+                                        C.c_void_p(d_lo_kind), C.c_void_p(d_hi_keys),
+                                        C.c_void_p(d_hi_pos), C.c_void_p(d_hi_kind), n_scans, limit,
+                                        *ptrs, C.c_void_p(stream)), "tpz_lsm_scan_ranges")
+
+    def lsm_scan_entries_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                              n_scans: int, limit: int, d_hit_table: int, d_hit_block: int,
+                              d_hit_entry: int, d_first: int, d_keys: int, key_cap: int,
+                              d_kpos: int, d_vals: int, val_cap: int, d_vpos: int,
+                              stream: int = 0) -> None:
+        """tpz_lsm_scan_entries: the entries tpz_lsm_scan_ranges yielded, from runs and tables."""
+        check(lib().tpz_lsm_scan_entries(self.handle, C.c_void_p(d_runs), n_runs,
+                                         C.c_void_p(d_tables), n_tables, n_scans, limit,
+                                         C.c_void_p(d_hit_table), C.c_void_p(d_hit_block),
+                                         C.c_void_p(d_hit_entry), C.c_void_p(d_first),
+                                         C.c_void_p(d_keys), key_cap, C.c_void_p(d_kpos),
+                                         C.c_void_p(d_vals), val_cap, C.c_void_p(d_vpos),
+                                         C.c_void_p(stream)), "tpz_lsm_scan_entries")
 
     def scan_ranges_ptrs(self, d_tables: int, n_tables: int, h_level_first: int, n_levels: int,
                          d_lo_keys: int, d_lo_pos: int, d_lo_kind: int, d_hi_keys: int,

@@ -13,6 +13,11 @@ LsmIterator drops them, and compaction does not use it.
 over the merged entries (tpz_entries_bound), SsTableBuilder's table cuts (tpz_table_cut) and every
 output table as a whole SST file image in one device arena (tpz_sst_finish); `sub_ranges` restates
 RwsSlice::create + split (src/level/range.rs) on the host.
+
+`flush_runs` is the write side of the memtables (start_flush and sync(), src/lsm_storage.rs:83-143,
+:298-332): sorted memtable runs in HBM merged (tpz_merge_runs) into one L0 file image with the
+same plan, encode, bloom and tpz_sst_finish steps; `flush_like_start_flush` and `flush_like_sync`
+state the two orders the reference merges them in.
 """
 from __future__ import annotations
 
@@ -374,6 +379,117 @@ def _window_bytes(ent: DeviceEntries, start: int, n: int, s) -> int:
     p = torch.stack((ent.kpos[start], ent.kpos[start + n], ent.vpos[start], ent.vpos[start + n]))
     k0, k1, v0, v1 = (int(x) for x in p.cpu())
     return k1 - k0 + v1 - v0
+
+
+# ------------------------------------------------------------------------- memtable flush
+def _run_columns(r):
+    """(keys, kpos, vals, vpos) of a run: a levels.DeviceRun or a DeviceEntries."""
+    return r.keys, r.kpos, r.vals, r.vpos
+
+
+def flush_runs(ctx: Context, runs, block_size: int = 4096, codec: int = 1,
+               false_positive_rate: float = 0.1, stream: torch.cuda.Stream | None = None):
+    """Sorted memtable runs in HBM -> one L0 SST file image (an OutputTable whose `image` is a
+    device tensor ready for one D2H copy), or None when the runs hold no entry (sync() builds
+    nothing from an empty map, lsm_storage.rs:316-318); otherwise (table, merged): the table and
+    the merged DeviceEntries its blocks hold.
+
+    `runs`: levels.DeviceRun (or DeviceEntries) objects in priority order: tpz_merge_runs lets the
+    LOWER index win a repeated key. Their columns are concatenated on the device with kpos / vpos
+    rebased, merged, and built into one table with no capacity cut: SsTableBuilder in start_flush
+    and sync() never tests reach_capacity. An empty key raises EntryError as tpz_plan_blocks
+    reports it (BlockBuilder::add asserts, builder.rs:27). Tombstones are kept."""
+    if codec not in (1, 2, 3):
+        raise ValueError(f"codec {codec}")
+    dev = _dev(ctx.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        return _flush_runs(ctx, list(runs), block_size, codec, false_positive_rate, s)
+
+
+def _flush_runs(ctx: Context, runs, block_size: int, codec: int, false_positive_rate: float, s):
+    dev = _dev(ctx.device)
+    keys, kpos, vals, vpos, run_first, koff, voff = [], [], [], [], [0], 0, 0
+    for r in runs:
+        k, kp, v, vp = _run_columns(r)
+        n = int(kp.numel()) - 1
+        kb, vb = (int(x) for x in torch.stack((kp[n], vp[n])).cpu())
+        keys.append(k[:kb])
+        vals.append(v[:vb])
+        kpos.append(kp[:n] + koff)
+        vpos.append(vp[:n] + voff)
+        koff, voff = koff + kb, voff + vb
+        run_first.append(run_first[-1] + n)
+    n = run_first[-1]
+    if n == 0:
+        return None
+    end = torch.tensor([koff, voff], dtype=torch.int64, device=dev)
+    pad = torch.zeros(16, dtype=torch.uint8, device=dev)     # (a column is never empty)
+    ent = DeviceEntries(torch.cat(keys + [pad]), torch.cat(kpos + [end[:1]]),
+                        torch.cat(vals + [pad]), torch.cat(vpos + [end[1:]]), ctx.device)
+    merged = merge_runs(ctx, ent, run_first, s)[0]
+    first, ext, info = plan_blocks_async(ctx, merged, block_size, s)
+    has_bloom = math.copysign(1.0, false_positive_rate) > 0          # is_sign_positive
+    n_out = merged.n
+    flen = 0
+    if has_bloom:
+        geo = _lib.bloom_geometry(n_out, false_positive_rate)
+        if geo is None:             # fpp 0 (`% limit` divides by zero) or >= 1 (bloom.rs:49)
+            raise ReferencePanic(f"no bloom filter for {n_out} keys at fpp {false_positive_rate}")
+        flen = geo[0]
+    data_bound = encode_bound(merged)
+    if codec != 1:
+        data_bound = compress_bound(data_bound, n_out)
+    arena = torch.empty(data_bound + 6 * n_out + int(merged.keys.numel()) + flen + 12 + 16 + 256,
+                        dtype=torch.uint8, device=dev)
+    plain = arena if codec == 1 else torch.empty(encode_bound(merged), dtype=torch.uint8, device=dev)
+    encode_blocks_async(ctx, merged, first, ext, info, plain, s)
+    _, bad, nb = (int(x) for x in info[:3].cpu().numpy().view(np.uint32))   # (waits for the stream)
+    if bad != 0xFFFFFFFF:
+        raise EntryError(bad, f"entry exceeds block_size {block_size} - 2")
+    data = int(ext[nb].cpu())
+    cext = ext
+    if codec != 1:
+        comp, cext = compress_blocks(ctx, plain, ext, nb, data, codec, stream=s)
+        data = int(cext[nb].cpu())
+        arena[:data].copy_(comp[:data])
+    filt = None
+    if has_bloom:
+        filt = torch.empty((flen + 3) // 4, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().tpz_bloom_build(
+            ctx.handle, C.c_void_p(merged.keys.data_ptr()), C.c_void_p(merged.kpos.data_ptr()),
+            n_out, false_positive_rate, C.c_void_p(filt.data_ptr()), C.c_void_p(s.cuda_stream)),
+            "tpz_bloom_build")
+    desc = _lib.SstImage(arena.data_ptr(), data, first.data_ptr(), cext.data_ptr(), nb, 0,
+                         filt.data_ptr() if filt is not None else None, flen)
+    d_desc = torch.from_numpy(np.frombuffer(bytes(desc), np.uint8).copy()).to(dev)
+    out = torch.empty(4, dtype=torch.int64, device=dev)
+    ctx.sst_finish_ptrs(merged.struct(), d_desc.data_ptr(), 1, nb, arena.data_ptr(),
+                        int(arena.numel()), out.data_ptr(), s.cuda_stream)
+    g = out.cpu().numpy().view(np.uint64)                                 # (waits for the stream)
+    size, boff = int(g[0]), int(g[2])
+    if size == 0 or size > arena.numel():
+        raise _lib.TpzError(f"tpz_sst_finish: the image has {size} bytes")
+    t = OutputTable(arena[:size], size, int(g[1]), None if boff == 2**64 - 1 else boff, nb, 0,
+                    n_out)
+    return t, merged
+
+
+def flush_like_start_flush(ctx: Context, view, block_size: int = 4096, codec: int = 1,
+                           false_positive_rate: float = 0.1, stream=None):
+    """start_flush (src/lsm_storage.rs:83-143): `view` is MemTables::view() as runs (the immutable
+    memtables oldest first, the mutable one last); the immutable ones are handed to
+    MergeIterator::create oldest first (:91-101), so the OLDEST memtable wins a repeated key. That
+    is the reference's behaviour, kept here. Returns flush_runs' (table, merged entries) or None."""
+    return flush_runs(ctx, list(view)[:-1], block_size, codec, false_positive_rate, stream)
+
+
+def flush_like_sync(ctx: Context, view, block_size: int = 4096, codec: int = 1,
+                    false_positive_rate: float = 0.1, stream=None):
+    """sync() (src/lsm_storage.rs:298-332): use_new_table() first makes every memtable of `view`
+    immutable; they are inserted into a BTreeMap oldest first (:306-314), so the NEWEST wins a
+    repeated key: the runs go to the merge newest first. An empty map builds nothing (None)."""
+    return flush_runs(ctx, list(view)[::-1], block_size, codec, false_positive_rate, stream)
 
 
 # ------------------------------------------------------------------------- the task's ranges

@@ -1097,6 +1097,80 @@ tpz_err tpz_get_values(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tab
   return TPZ_SUCCESS;
 }
 
+// tpz_lsm_get_keys / tpz_lsm_get_values: d_runs holds n_runs <= TPZ_MEM_MAX_RUNS descriptors.
+static bool runs_ok(const tpz_mem_run* d_runs, uint32_t n_runs) {
+  return n_runs <= TPZ_MEM_MAX_RUNS && (n_runs == 0 || d_runs) && !((uintptr_t)d_runs & 7u);
+}
+
+tpz_err tpz_mem_prefix(tpz_ctx* c, const tpz_entries* entries, uint64_t* d_prefix, void* stream) {
+  if (!c || !entries) return TPZ_ERR_INVALID_ARG;
+  if (entries->n_entries == 0) return TPZ_SUCCESS;
+  if (!d_prefix || !entries->d_kpos || (entries->key_bytes && !entries->d_keys) ||
+      (((uintptr_t)d_prefix | (uintptr_t)entries->d_kpos) & 7u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::launch_mem_prefix(*entries, d_prefix, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_lsm_get_keys(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                         const tpz_get_table* d_tables, uint32_t n_tables,
+                         const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                         const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                         uint8_t* d_status, uint32_t* d_table, uint32_t* d_block,
+                         uint32_t* d_entry, uint64_t* d_val_pos, void* stream) {
+  if (!c || !d_key_pos || !d_result || !d_status || !d_table || !d_block || !d_entry || !d_val_pos ||
+      (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
+    return TPZ_ERR_INVALID_ARG;
+  if (!level_first_ok(h_level_first, n_levels, n_tables) || n_keys == 0xFFFFFFFFu)
+    return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_tables | (uintptr_t)d_key_pos | (uintptr_t)d_val_pos) & 7u) ||
+      (((uintptr_t)d_table | (uintptr_t)d_block | (uintptr_t)d_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_keys == 0) {
+    TPZ_HIP(hipMemsetAsync(d_val_pos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* part = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_get, &w.get_cap, 8 * (tpz::flat_scan_parts_words(n_keys) / 3));
+    if (r != TPZ_SUCCESS) return r;
+    part = w.d_get;
+  }
+  tpz::LsmGetLaunch a{{d_tables, n_tables, h_level_first, n_levels, d_keys, d_key_pos, n_keys,
+                       d_result, d_status, d_table, d_block, d_entry, d_val_pos,
+                       static_cast<uint64_t*>(part)}, d_runs, n_runs};
+  tpz::launch_lsm_get_walk(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_lsm_get_values(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                           const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_keys,
+                           const uint8_t* d_result, const uint32_t* d_table,
+                           const uint32_t* d_block, const uint32_t* d_entry,
+                           const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
+                           void* stream) {
+  if (!c || (n_tables && !d_tables) || (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
+      (n_keys && (!d_result || !d_table || !d_block || !d_entry || !d_val_pos)))
+    return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_vals & 15u) || (((uintptr_t)d_tables | (uintptr_t)d_val_pos) & 7u) ||
+      (((uintptr_t)d_table | (uintptr_t)d_block | (uintptr_t)d_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  if (n_keys == 0 || val_cap == 0) return TPZ_SUCCESS;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::LsmGetGatherLaunch a{{d_tables, n_tables, n_keys, d_result, d_table, d_block, d_entry,
+                             d_val_pos, d_vals, val_cap}, d_runs, n_runs};
+  tpz::launch_lsm_get_gather(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
 // limit >= 1 and n_scans * limit < 2^32 (the hit columns are indexed with it).
 static bool scan_shape_ok(uint32_t n_tables, uint32_t n_scans, uint32_t limit) {
   return n_tables <= TPZ_SCAN_MAX_TABLES && limit != 0 &&
@@ -1184,6 +1258,95 @@ tpz_err tpz_scan_entries(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_t
                            d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals, val_cap, d_vpos,
                            work};
   tpz::launch_scan_entries(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_lsm_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                            const tpz_get_table* d_tables, uint32_t n_tables,
+                            const uint32_t* h_level_first, uint32_t n_levels,
+                            const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                            const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                            const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans,
+                            uint32_t limit, uint8_t* d_result, uint8_t* d_status,
+                            uint32_t* d_where, uint32_t* d_hit_table, uint32_t* d_hit_block,
+                            uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
+                            uint64_t* d_val_first, uint64_t* d_info, void* stream) {
+  if (!c || !d_lo_pos || !d_lo_kind || !d_hi_pos || !d_hi_kind || !d_result || !d_status ||
+      !d_where || !d_hit_table || !d_hit_block || !d_hit_entry || !d_first || !d_key_first ||
+      !d_val_first || !d_info || (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
+    return TPZ_ERR_INVALID_ARG;
+  if (!scan_shape_ok(n_tables, n_scans, limit) || n_runs + n_tables > TPZ_SCAN_MAX_TABLES ||
+      !level_first_ok(h_level_first, n_levels, n_tables))
+    return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_tables | (uintptr_t)d_lo_pos | (uintptr_t)d_hi_pos | (uintptr_t)d_first |
+        (uintptr_t)d_key_first | (uintptr_t)d_val_first | (uintptr_t)d_info) & 7u) ||
+      (((uintptr_t)d_where | (uintptr_t)d_hit_table | (uintptr_t)d_hit_block |
+        (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_key_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_val_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap,
+                     tpz::scan_ranges_work_bytes(n_scans, n_runs + n_tables));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_scan;
+  }
+  tpz::LsmScanLaunch a{{d_tables, n_tables, n_levels ? h_level_first[1] : 0u, d_lo_keys, d_lo_pos,
+                        d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit, d_result,
+                        d_status, d_where, d_hit_table, d_hit_block, d_hit_entry, d_first,
+                        d_key_first, d_val_first, d_info, work}, d_runs, n_runs};
+  tpz::launch_lsm_scan_ranges(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_lsm_scan_entries(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                             const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_scans,
+                             uint32_t limit, const uint32_t* d_hit_table,
+                             const uint32_t* d_hit_block, const uint32_t* d_hit_entry,
+                             const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
+                             uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
+                             void* stream) {
+  if (!c || !d_kpos || !d_vpos || (n_tables && !d_tables) || (key_cap && !d_keys) ||
+      (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
+      (n_scans && (!d_hit_table || !d_hit_block || !d_hit_entry || !d_first)))
+    return TPZ_ERR_INVALID_ARG;
+  if (!scan_shape_ok(n_tables, n_scans, limit) || n_runs + n_tables > TPZ_SCAN_MAX_TABLES)
+    return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
+      (((uintptr_t)d_tables | (uintptr_t)d_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u) ||
+      (((uintptr_t)d_hit_table | (uintptr_t)d_hit_block | (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_entries_work_bytes(n_scans));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_scan;
+  }
+  tpz::LsmScanEntriesLaunch a{{d_tables, n_tables, n_scans, limit, d_hit_table, d_hit_block,
+                               d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals, val_cap,
+                               d_vpos, work}, d_runs, n_runs};
+  tpz::launch_lsm_scan_entries(a, s);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }

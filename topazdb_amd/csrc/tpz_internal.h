@@ -368,6 +368,22 @@ struct GetGatherLaunch {
 };
 void launch_get_gather(const GetGatherLaunch& a, hipStream_t stream);
 
+// tpz_mem_prefix / tpz_lsm_get_keys / tpz_lsm_get_values (tpz_mem.hip): memtable runs resident in
+// HBM, and LsmStorage::get over them plus the tables.
+void launch_mem_prefix(const tpz_entries& e, uint64_t* prefix, hipStream_t stream);   // n_entries > 0
+struct LsmGetLaunch {
+  GetLaunch get;
+  const tpz_mem_run* runs;      // device
+  uint32_t n_runs;              // <= TPZ_MEM_MAX_RUNS
+};
+void launch_lsm_get_walk(const LsmGetLaunch& a, hipStream_t stream);
+struct LsmGetGatherLaunch {
+  GetGatherLaunch get;
+  const tpz_mem_run* runs;
+  uint32_t n_runs;
+};
+void launch_lsm_get_gather(const LsmGetGatherLaunch& a, hipStream_t stream);
+
 // tpz_scan_ranges / tpz_scan_entries (tpz_scan.hip): LsmStorage::scan's SST half over resident
 // tables.
 struct ScanLaunch {
@@ -415,6 +431,23 @@ struct ScanEntriesLaunch {
 };
 uint64_t scan_entries_work_bytes(uint32_t n_scans);
 void launch_scan_entries(const ScanEntriesLaunch& a, hipStream_t stream);
+// The scans of d_first / d_key_first / d_val_first and d_info (the tail of launch_scan_ranges).
+void launch_scan_totals(const ScanLaunch& a, uint64_t* part, hipStream_t stream);
+// tpz_lsm_scan_ranges / tpz_lsm_scan_entries (tpz_mem.hip): LsmStorage::scan whole, the memtable
+// runs' cursors in front of the tables'. work: scan_ranges_work_bytes(n_scans, n_runs + n_tables)
+// / scan_entries_work_bytes(n_scans).
+struct LsmScanLaunch {
+  ScanLaunch scan;
+  const tpz_mem_run* runs;      // device
+  uint32_t n_runs;              // <= TPZ_MEM_MAX_RUNS, n_runs + n_tables <= TPZ_SCAN_MAX_TABLES
+};
+void launch_lsm_scan_ranges(const LsmScanLaunch& a, hipStream_t stream);
+struct LsmScanEntriesLaunch {
+  ScanEntriesLaunch scan;
+  const tpz_mem_run* runs;
+  uint32_t n_runs;
+};
+void launch_lsm_scan_entries(const LsmScanEntriesLaunch& a, hipStream_t stream);
 
 // tpz_entries_bound / tpz_table_cut / tpz_sst_finish (tpz_tables.hip): a compaction task's key
 // ranges, table cuts and SST file images.

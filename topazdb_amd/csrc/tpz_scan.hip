@@ -36,345 +36,26 @@
 
 #include "tpz_copy.h"
 #include "tpz_internal.h"
-#include "tpz_seek_dev.h"
+#include "tpz_scan_dev.h"
 
 namespace tpz {
 
 namespace {
 
+using scandev::EntriesParams;
+using scandev::kWaves;
+using scandev::MergeParams;
+using scandev::SeekParams;
 using seekdev::u32;
 using seekdev::u64;
 
-constexpr u32 kNone = 0xFFFFFFFFu;
-constexpr u64 kLaneCopyMax = 256;   // the get gather's threshold (tpz_get.hip)
-constexpr u32 kUnopened = 0x80u;    // cursor status flag: the table could not have been opened
-constexpr u32 kWaves = 4;           // scans per workgroup of the wave-per-scan kernels
-
-// Cursor `p` of a scan in priority order -> index into d_tables (level.rs:570-577: L0 reversed,
-// then every level as stored). l0 = the number of L0 tables.
-__device__ __forceinline__ u32 table_of(u32 p, u32 l0) { return p < l0 ? l0 - 1 - p : p; }
-
-// An SsTableIterator's position and what the merge reads there.
-struct Cur {
-  u32 b, e, n;             // block, entry, the block's entry count
-  seekdev::BlockView v;    // block b
-  const uint8_t* key;
-  u64 klen, vlen;
-};
-enum : u32 { kValid = 0, kInvalid = 1, kFail = 2 };   // kFail: (c.b, c.e) and `fst` say where / what
-
-// BlockIterator::seek_to(c.e) in the open block (block/iterator.rs:74-82) and is_valid().
-__device__ __forceinline__ u32 land(Cur& c, u32& fst) {
-  if (c.e >= c.n) return kInvalid;
-  if (c.v.seek_panics(c.e)) {
-    fst = TPZ_BLOCK_MALFORMED;
-    return kFail;
-  }
-  c.key = seekdev::entry_key(c.v, c.e, c.klen);
-  if (c.klen == 0) return kInvalid;
-  seekdev::entry_value(c.v, c.n, c.e, c.vlen);
-  return kValid;
-}
-__device__ __forceinline__ void open_block(const tpz_table& t, Cur& c, u32 b, u32 st) {
-  c.b = b;
-  c.n = t.d_count[b];
-  c.v = seekdev::block_view(t, b, st);
-}
-// SsTableIterator::seek_to_first_inner(table, b) (table/iterator.rs:39-42).
-__device__ __forceinline__ u32 first_of_block(const tpz_table& t, Cur& c, u32 b, u32& fst) {
-  c.b = b;
-  c.e = 0;
-  const u32 st = t.d_status[b];
-  if (!block_decoded(st)) {
-    fst = st;
-    return kFail;
-  }
-  open_block(t, c, b, st);
-  return land(c, fst);
-}
-// SsTableIterator::next (table/iterator.rs:88-95) of a valid cursor.
-__device__ __forceinline__ u32 advance(const tpz_table& t, Cur& c, u32& fst) {
-  c.e++;
-  u32 r = land(c, fst);
-  if (r == kInvalid && c.b + 1 < t.n_blocks) r = first_of_block(t, c, c.b + 1, fst);
-  return r;
-}
-
-// SsTable::open's init_samllest_biggest_key (table.rs:143-151): the last entry's key of the last
-// block. False where the reference fails there: `fst` and `fb` (the block, or kNone) say how.
-__device__ __forceinline__ bool biggest_key(const tpz_table& t, const uint8_t*& k, u64& kl,
-                                            u32& fst, u32& fb) {
-  fst = TPZ_BLOCK_MALFORMED;
-  fb = kNone;
-  if (t.n_blocks == 0) return false;             // block_metas[0]
-  const u32 b = t.n_blocks - 1;
-  fb = b;
-  const u32 st = t.d_status[b];
-  if (!block_decoded(st)) {                      // read_block(..)?
-    fst = st;
-    return false;
-  }
-  const u32 n = t.d_count[b];
-  if (n == 0) return false;                      // seek_to_last: offsets.len() - 1
-  const seekdev::BlockView v = seekdev::block_view(t, b, st);
-  if (v.seek_panics(0) || v.seek_panics(n - 1)) return false;   // seek_to_first, seek_to_last
-  k = seekdev::entry_key(v, n - 1, kl);
-  return kl > 0;                                 // assert!(iter.is_valid())
-}
-
-struct SeekParams {
-  const tpz_get_table* tabs;
-  u32 n_tables;
-  u32 l0;
-  const uint8_t* lo;
-  const u64* lo_pos;
-  const uint8_t* lo_kind;
-  const uint8_t* hi;
-  const u64* hi_pos;
-  const uint8_t* hi_kind;
-  u32 n_scans;
-  u32* cur;          // 2 x n_scans x n_tables
-  uint8_t* cst;      // n_scans x n_tables
-};
-
+// The bodies are tpz_scan_dev.h's, without the memtable side (tpz_mem.hip runs them with it).
 __global__ __launch_bounds__(256) void scan_seek_kernel(SeekParams p) {
-  const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (g >= (u64)p.n_scans * p.n_tables) return;
-  const u32 i = (u32)(g / p.n_tables);
-  const u32 t = table_of((u32)(g % p.n_tables), p.l0);
-  const u32 lk = p.lo_kind[i], hk = p.hi_kind[i];
-  u32 b = kNone, e = kNone, cs = TPZ_BLOCK_OK;
-  if (lk <= TPZ_BOUND_AFTER && hk <= TPZ_BOUND_EXCLUDED) {   // (else the merge reports the kind)
-    const tpz_table& tab = p.tabs[t].table;
-    const uint8_t* big = nullptr;
-    u64 bigl = 0;
-    u32 fst, fb;
-    if (!biggest_key(tab, big, bigl, fst, fb)) {
-      cs = fst | kUnopened;
-      b = fb;
-    } else {
-      const u64 la = p.lo_pos[i], ha = p.hi_pos[i];
-      const uint8_t* lo = p.lo + la;
-      const uint8_t* hi = p.hi + ha;
-      const u64 lol = p.lo_pos[i + 1] - la, hil = p.hi_pos[i + 1] - ha;
-      // level_tables_sorted's filter (level.rs:554-568)
-      bool keep = lk == TPZ_BOUND_UNBOUNDED || seekdev::key_cmp(big, bigl, lo, lol) >= 0;
-      if (keep && hk != TPZ_BOUND_UNBOUNDED) {
-        const u64 sa = tab.d_first_pos[0];
-        keep = seekdev::key_cmp(tab.d_first_keys + sa, tab.d_first_pos[1] - sa, hi, hil) <= 0;
-      }
-      if (keep) {
-        Cur c;
-        u32 r;
-        if (lk == TPZ_BOUND_UNBOUNDED) {           // create_and_seek_to_first
-          r = first_of_block(tab, c, 0, fst);
-        } else {                                   // create_and_seek_to_key
-          const seekdev::SeekPos s = seekdev::seek_table(tab, lo, lol);
-          c.b = s.block;
-          c.e = s.entry;
-          fst = s.status;
-          r = s.status != TPZ_BLOCK_OK ? kFail : s.valid ? kValid : kInvalid;
-          if (r == kValid && lk != TPZ_BOUND_INCLUDED) {   // lsm_storage.rs:356-362
-            open_block(tab, c, c.b, tab.d_status[c.b]);
-            c.key = seekdev::entry_key(c.v, c.e, c.klen);
-            if (c.klen == lol && seekdev::key_cmp(c.key, c.klen, lo, lol) == 0)
-              r = advance(tab, c, fst);
-          }
-        }
-        if (r != kInvalid) {
-          b = c.b;
-          e = c.e;
-        }
-        if (r == kFail) cs = fst;
-      }
-    }
-  }
-  p.cur[2 * g] = b;
-  p.cur[2 * g + 1] = e;
-  p.cst[g] = (uint8_t)cs;
+  scandev::seek_body<false>(p, scandev::Runs{nullptr, 0});
 }
-
-// The first 8 bytes of a key, big-endian, zero-padded: orders keys as memcmp does wherever two
-// prefixes differ.
-__device__ __forceinline__ u64 key_prefix(const uint8_t* k, u64 len) {
-  u64 x = 0;
-  const u32 n = len < 8 ? (u32)len : 8u;
-  for (u32 j = 0; j < n; j++) x |= (u64)k[j] << (56 - 8 * j);
-  return x;
-}
-// key_cmp for two keys whose key_prefix is equal: with a key of at most 8 bytes the shorter one
-// is a prefix of the other (`a` against `a\0`: the padding is not part of the key), else the
-// bytes after the eighth decide.
-__device__ __forceinline__ int cmp_tied(const uint8_t* a, u64 al, const uint8_t* b, u64 bl) {
-  if (al <= 8 || bl <= 8) return al < bl ? -1 : (al > bl ? 1 : 0);
-  return seekdev::key_cmp(a + 8, al - 8, b + 8, bl - 8);
-}
-__device__ __forceinline__ const uint8_t* shfl_ptr(const uint8_t* p, int l) {
-  return reinterpret_cast<const uint8_t*>((uintptr_t)__shfl((u64)(uintptr_t)p, l, 64));
-}
-
-struct MergeParams {
-  const tpz_get_table* tabs;
-  u32 n_tables;
-  u32 l0;
-  const uint8_t* hi;
-  const u64* hi_pos;
-  const uint8_t* lo_kind;
-  const uint8_t* hi_kind;
-  u32 n_scans;
-  u32 limit;
-  const u32* cur;
-  const uint8_t* cst;
-  uint8_t* result;
-  uint8_t* status;
-  u32* where;
-  u32* hit_table;
-  u32* hit_block;
-  u32* hit_entry;
-  u64* first;
-  u64* key_first;
-  u64* val_first;
-};
 
 __global__ __launch_bounds__(256) void scan_merge_kernel(MergeParams p) {
-  const u32 lane = copydev::lane_id();
-  const u32 i = blockIdx.x * kWaves + threadIdx.x / 64;
-  if (i >= p.n_scans) return;                    // (the whole wave)
-  const u32 lk = p.lo_kind[i], hk = p.hi_kind[i];
-  u32 res = TPZ_SCAN_DONE, st = TPZ_BLOCK_OK, w0 = kNone, w1 = kNone, w2 = kNone, count = 0;
-  u64 kb = 0, vb = 0;
-  if (lk > TPZ_BOUND_AFTER || hk > TPZ_BOUND_EXCLUDED) {
-    res = TPZ_SCAN_ERROR;
-    st = TPZ_BLOCK_MALFORMED;
-  } else {
-    Cur c;
-    c.b = c.e = kNone;
-    c.n = 0;
-    c.key = nullptr;
-    c.klen = c.vlen = 0;
-    u32 cs = TPZ_BLOCK_OK, t = 0;
-    const tpz_table* tab = nullptr;
-    if (lane < p.n_tables) {
-      t = table_of(lane, p.l0);
-      const u64 g = (u64)i * p.n_tables + lane;
-      c.b = p.cur[2 * g];
-      c.e = p.cur[2 * g + 1];
-      cs = p.cst[g];
-      tab = &p.tabs[t].table;
-    }
-    // Failures while the cursors are created: a table that could not have been opened is found
-    // by the filter, before any seek; either way the first one in priority order is reported.
-    const u64 unopened = __ballot((cs & kUnopened) != 0), failed = __ballot(cs != TPZ_BLOCK_OK);
-    if (failed) {
-      const int f = __builtin_ctzll(unopened ? unopened : failed);
-      res = TPZ_SCAN_ERROR;
-      st = __shfl(cs & ~kUnopened, f, 64);
-      w0 = __shfl(t, f, 64);
-      w1 = __shfl(c.b, f, 64);
-      w2 = __shfl(c.e, f, 64);
-    } else {
-      // MergeIterator::create keeps the valid cursors (merge_iterator.rs:47-57)
-      bool live = false;
-      if (tab && c.b < tab->n_blocks) {
-        const u32 bst = tab->d_status[c.b];
-        if (block_decoded(bst)) {
-          open_block(*tab, c, c.b, bst);
-          u32 fst;
-          live = land(c, fst) == kValid;
-        }
-      }
-      u64 pfx = live ? key_prefix(c.key, c.klen) : 0;
-      const u64 ha = p.hi_pos[i];
-      const uint8_t* hi = p.hi + ha;
-      const u64 hil = p.hi_pos[i + 1] - ha;
-      bool e0 = lk != TPZ_BOUND_AFTER;           // element 0 is not end-checked
-      while (__ballot(live)) {
-        // the minimum (key, lane)
-        u64 m = live ? pfx : ~0ull;
-        for (int o = 32; o; o >>= 1) {
-          const u64 x = __shfl_xor(m, o, 64);
-          m = x < m ? x : m;
-        }
-        u64 tied = __ballot(live && pfx == m);
-        u64 eq = tied;
-        int ld = __builtin_ctzll(tied);
-        const uint8_t* lkey = shfl_ptr(c.key, ld);
-        u64 lklen = __shfl(c.klen, ld, 64);
-        if (tied & (tied - 1)) {
-          for (;;) {       // the candidate is the first lane of `tied`; lanes below it lost
-            int cmp = 1;
-            if ((tied >> lane) & 1) cmp = cmp_tied(c.key, c.klen, lkey, lklen);
-            const u64 less = __ballot(cmp < 0);
-            if (!less) {
-              eq = __ballot(cmp == 0);
-              break;
-            }
-            tied = less;
-            ld = __builtin_ctzll(tied);
-            lkey = shfl_ptr(c.key, ld);
-            lklen = __shfl(c.klen, ld, 64);
-          }
-        }
-        const u64 lvlen = __shfl(c.vlen, ld, 64);
-        // LsmIterator::next_inner's end check (lsm_iterator.rs:46-50), tombstones included
-        if (!e0 && hk != TPZ_BOUND_UNBOUNDED) {
-          const int cc = seekdev::key_cmp(lkey, lklen, hi, hil);
-          if (hk == TPZ_BOUND_INCLUDED ? cc > 0 : cc >= 0) break;
-        }
-        e0 = false;
-        if (lvlen) {                              // (an empty value is skipped)
-          if (count == p.limit) {
-            res = TPZ_SCAN_MORE;
-            break;
-          }
-          if (lane == (u32)ld) {
-            const u64 h = (u64)i * p.limit + count;
-            p.hit_table[h] = t;
-            p.hit_block[h] = c.b;
-            p.hit_entry[h] = c.e;
-          }
-          count++;
-          kb += lklen;
-          vb += lvlen;
-        }
-        // MergeIterator::next: the other cursors at this key first, the current one last
-        u32 r = kValid, fst = TPZ_BLOCK_OK;
-        if ((eq >> lane) & 1) {
-          if (lane == (u32)ld) {
-            r = advance(*tab, c, fst);
-          } else {
-            do {
-              r = advance(*tab, c, fst);
-            } while (r == kValid && c.klen == lklen &&
-                     seekdev::key_cmp(c.key, c.klen, lkey, lklen) == 0);
-          }
-          live = r == kValid;
-          if (live) pfx = key_prefix(c.key, c.klen);
-        }
-        const u64 fails = __ballot(r == kFail);
-        if (fails) {
-          const u64 others = fails & ~(1ull << ld);
-          const int f = __builtin_ctzll(others ? others : fails);
-          res = TPZ_SCAN_ERROR;
-          st = __shfl(fst, f, 64);
-          w0 = __shfl(t, f, 64);
-          w1 = __shfl(c.b, f, 64);
-          w2 = __shfl(c.e, f, 64);
-          break;
-        }
-      }
-    }
-  }
-  if (lane == 0) {
-    p.result[i] = (uint8_t)res;
-    p.status[i] = (uint8_t)st;
-    p.where[3 * (u64)i] = w0;
-    p.where[3 * (u64)i + 1] = w1;
-    p.where[3 * (u64)i + 2] = w2;
-    p.first[i] = count;
-    p.key_first[i] = kb;
-    p.val_first[i] = vb;
-  }
+  scandev::merge_body<false>(p, scandev::Runs{nullptr, 0});
 }
 
 __global__ void scan_info_kernel(const u64* first, const u64* key_first, const u64* val_first,
@@ -386,97 +67,9 @@ __global__ void scan_info_kernel(const u64* first, const u64* key_first, const u
   }
 }
 
-struct EntriesParams {
-  const tpz_get_table* tabs;
-  u32 n_tables;
-  u32 n_scans;
-  u32 limit;
-  const u32* hit_table;
-  const u32* hit_block;
-  const u32* hit_entry;
-  const u64* first;
-  u64* kbase;        // n_scans + 1: the scans' key bytes, scanned in place between the passes
-  u64* vbase;
-  uint8_t* keys;
-  u64 key_cap;
-  u64* kpos;
-  uint8_t* vals;
-  u64 val_cap;
-  u64* vpos;
-};
-
-__device__ __forceinline__ void wave_copies(uint8_t* dst, u64 cap, u64 d, const uint8_t* src,
-                                            u64 len, u32 lane) {
-  if (len && len <= kLaneCopyMax) copydev::lane_copy(dst, cap, d, src, len);
-  u64 mask = __ballot(len > kLaneCopyMax);
-  while (mask) {
-    const int l = __builtin_ctzll(mask);
-    mask &= mask - 1;
-    copydev::wave_copy(dst, cap, __shfl(d, l, 64), shfl_ptr(src, l), __shfl(len, l, 64), lane);
-  }
-}
-
 template <bool kCopy>
 __global__ __launch_bounds__(256) void scan_entries_kernel(EntriesParams p) {
-  const u32 lane = copydev::lane_id();
-  const u32 i = blockIdx.x * kWaves + threadIdx.x / 64;
-  if (i >= p.n_scans) return;
-  const u64 f0 = p.first[i], f1 = p.first[i + 1], total = p.first[p.n_scans];
-  u64 cnt = f1 > f0 ? f1 - f0 : 0;
-  if (cnt > p.limit) cnt = p.limit;
-  if (f0 >= total) cnt = 0;
-  else if (cnt > total - f0) cnt = total - f0;
-  u64 kb = kCopy ? p.kbase[i] : 0, vb = kCopy ? p.vbase[i] : 0;
-  for (u64 c0 = 0; c0 < cnt; c0 += 64) {
-    const u64 j = c0 + lane;
-    const uint8_t* ksrc = nullptr;
-    const uint8_t* vsrc = nullptr;
-    u64 kl = 0, vl = 0;
-    if (j < cnt) {
-      const u64 h = (u64)i * p.limit + j;
-      const u32 t = p.hit_table[h], b = p.hit_block[h], e = p.hit_entry[h];
-      if (t < p.n_tables) {
-        const tpz_table& tab = p.tabs[t].table;
-        if (b < tab.n_blocks) {
-          const u32 st = tab.d_status[b];
-          const u32 n = tab.d_count[b];
-          if (block_decoded(st) && e < n) {
-            const seekdev::BlockView v = seekdev::block_view(tab, b, st);
-            ksrc = seekdev::entry_key(v, e, kl);
-            vsrc = seekdev::entry_value(v, n, e, vl);
-          }
-        }
-      }
-    }
-    u64 ks = kl, vs = vl;                          // inclusive sums over the wave
-    for (u32 o = 1; o < 64; o <<= 1) {
-      const u64 a = __shfl_up(ks, o, 64), c = __shfl_up(vs, o, 64);
-      if (lane >= o) {
-        ks += a;
-        vs += c;
-      }
-    }
-    if (kCopy) {
-      const u64 kd = kb + ks - kl, vd = vb + vs - vl;
-      if (j < cnt) {
-        p.kpos[f0 + j] = kd;
-        p.vpos[f0 + j] = vd;
-      }
-      wave_copies(p.keys, p.key_cap, kd, ksrc, kl, lane);
-      wave_copies(p.vals, p.val_cap, vd, vsrc, vl, lane);
-    }
-    kb += __shfl(ks, 63, 64);
-    vb += __shfl(vs, 63, 64);
-  }
-  if (lane == 0) {
-    if (!kCopy) {
-      p.kbase[i] = kb;
-      p.vbase[i] = vb;
-    } else if (i == p.n_scans - 1) {
-      p.kpos[total] = kb;
-      p.vpos[total] = vb;
-    }
-  }
+  scandev::entries_body<kCopy, false>(p, scandev::Runs{nullptr, 0});
 }
 
 }  // namespace
@@ -488,6 +81,14 @@ uint64_t scan_ranges_work_bytes(uint32_t n_scans, uint32_t n_tables) {
 
 uint64_t scan_entries_work_bytes(uint32_t n_scans) {
   return 8 * (2 * ((uint64_t)n_scans + 1) + flat_scan_parts_words(n_scans) / 3);
+}
+
+void launch_scan_totals(const ScanLaunch& a, uint64_t* part, hipStream_t stream) {
+  launch_scan_u64(a.first, a.n_scans, part, stream);
+  launch_scan_u64(a.key_first, a.n_scans, part, stream);
+  launch_scan_u64(a.val_first, a.n_scans, part, stream);
+  hipLaunchKernelGGL(scan_info_kernel, dim3(1), dim3(64), 0, stream, a.first, a.key_first,
+                     a.val_first, a.n_scans, a.info);
 }
 
 void launch_scan_ranges(const ScanLaunch& a, hipStream_t stream) {
@@ -505,11 +106,7 @@ void launch_scan_ranges(const ScanLaunch& a, hipStream_t stream) {
                 a.first, a.key_first, a.val_first};
   hipLaunchKernelGGL(scan_merge_kernel, dim3((a.n_scans + kWaves - 1) / kWaves), dim3(256), 0,
                      stream, m);
-  launch_scan_u64(a.first, a.n_scans, part, stream);
-  launch_scan_u64(a.key_first, a.n_scans, part, stream);
-  launch_scan_u64(a.val_first, a.n_scans, part, stream);
-  hipLaunchKernelGGL(scan_info_kernel, dim3(1), dim3(64), 0, stream, a.first, a.key_first,
-                     a.val_first, a.n_scans, a.info);
+  launch_scan_totals(a, part, stream);
 }
 
 void launch_scan_entries(const ScanEntriesLaunch& a, hipStream_t stream) {

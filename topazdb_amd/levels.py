@@ -18,8 +18,13 @@ descriptor per table once, and answers
   scan(lower, upper)
                     the reference's FusedIterator<LsmIterator>, pulled page by page
 
-There is no CPU fallback: the walk, the merge and the gathers are the kernels of csrc/tpz_get.hip
-and csrc/tpz_scan.hip.
+`DeviceRun(ctx, entries)` is one memtable's sorted snapshot in HBM (a tpz_mem_run, with its prefix
+column), and `DeviceLsm(ctx, runs, levels)` answers LsmStorage::get (src/lsm_storage.rs:198-213)
+and LsmStorage::scan (:335-374, the memtables merged in with TwoMergeIterator) over runs plus
+tables: `get_batch`, `get`, `scan_batch` and `scan` shaped exactly like DeviceLevels'.
+
+There is no CPU fallback: the walk, the merge and the gathers are the kernels of csrc/tpz_get.hip,
+csrc/tpz_scan.hip and csrc/tpz_mem.hip.
 """
 from __future__ import annotations
 
@@ -31,7 +36,7 @@ import torch
 from . import _lib
 from ._lib import (BLOCK_MALFORMED, BOUND_AFTER, BOUND_EXCLUDED, BOUND_INCLUDED, BOUND_UNBOUNDED,
                    GET_ABSENT, GET_DELETED, GET_ERROR, GET_FOUND, GET_NONE, SCAN_ERROR, SCAN_MORE,
-                   Context, GetTable)
+                   Context, Entries, GetTable, MemRun)
 from .table import DeviceTable, ReferencePanic, _pack
 
 
@@ -280,3 +285,153 @@ class DeviceLevels:
         assert res == GET_ERROR, res
         raise self.error(int(r["status"][0]), int(r["table"][0]), int(r["block"][0]),
                          int(r["entry"][0]))
+
+
+class DeviceRun:
+    """One memtable's SkipMap as a tpz_mem_run in HBM: `entries` is its (key, value) list in key
+    order (keys strictly increasing, an empty value a tombstone), or a dict of device columns
+    keys, kpos, vals, vpos (uint8 / int64 tensors; kpos and vpos hold n + 1 positions). With
+    `prefix` the prefix column is built on the device (tpz_mem_prefix); without it the lookups
+    bisect on the keys, with the same answers."""
+
+    def __init__(self, ctx: Context, entries, prefix: bool = True):
+        self.ctx = ctx
+        self.dev = torch.device("cuda", ctx.device)
+        if isinstance(entries, dict):
+            self.keys, self.kpos, self.vals, self.vpos = (entries[k] for k in
+                                                          ("keys", "kpos", "vals", "vpos"))
+            self.n = int(self.kpos.numel()) - 1
+            self.key_bytes, self.val_bytes = int(self.kpos[-1].item()), int(self.vpos[-1].item())
+        else:
+            entries = [(bytes(k), bytes(v)) for k, v in entries]
+            self.n = len(entries)
+            cols = []
+            for side in ([k for k, _ in entries], [v for _, v in entries]):
+                buf, pos = _pack(side)
+                cols += [torch.from_numpy(buf.copy()).to(self.dev), torch.from_numpy(pos).to(self.dev),
+                         int(pos[-1])]
+            self.keys, self.kpos, self.key_bytes, self.vals, self.vpos, self.val_bytes = cols
+        self.prefix = None
+        if prefix:
+            self.prefix = torch.empty(max(self.n, 1), dtype=torch.int64, device=self.dev)
+            ctx.mem_prefix_ptrs(self.entries(), self.prefix.data_ptr(),
+                                torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def entries(self) -> Entries:
+        return Entries(self.keys.data_ptr(), self.kpos.data_ptr(), self.vals.data_ptr(),
+                       self.vpos.data_ptr(), self.n, self.key_bytes, self.val_bytes)
+
+    def run(self) -> MemRun:
+        return MemRun(self.entries(), None if self.prefix is None else self.prefix.data_ptr())
+
+
+class DeviceLsm(DeviceLevels):
+    """LsmStorage::get and LsmStorage::scan over memtable runs plus the tables of a
+    LevelController: `runs` are DeviceRuns in MemTables::view() order (src/mem_table.rs:74-81: the
+    immutable memtables oldest first, the mutable one last; the last run has the highest
+    priority), `levels` as for DeviceLevels. A hit in run r is reported as table = HIT_MEM | r,
+    block 0, entry = its index in the run."""
+
+    def __init__(self, ctx: Context, runs: list, levels: list[list]):
+        if len(runs) > _lib.MEM_MAX_RUNS:
+            raise ValueError(f"{len(runs)} runs: at most {_lib.MEM_MAX_RUNS}")
+        super().__init__(ctx, levels)
+        if len(runs) + self.n_tables > _lib.SCAN_MAX_TABLES:
+            raise ValueError(f"{len(runs)} runs and {self.n_tables} tables: at most "
+                             f"{_lib.SCAN_MAX_TABLES} cursors")
+        self.runs = list(runs)
+        self.n_runs = len(self.runs)
+        desc = (MemRun * max(self.n_runs, 1))()
+        for i, r in enumerate(self.runs):
+            desc[i] = r.run()
+        raw = np.frombuffer(bytes(desc), np.uint8).copy()
+        self.d_runs = torch.from_numpy(raw).to(self.dev)         # uploaded once
+
+    def walk(self, keys: list[bytes]) -> dict:
+        """tpz_lsm_get_keys on the current stream: DeviceLevels.walk's outputs."""
+        n = len(keys)
+        buf, pos = _pack(keys)
+        q = torch.from_numpy(buf.copy()).to(self.dev)
+        qp = torch.from_numpy(pos).to(self.dev)
+        out = {k: torch.empty(max(n, 1), dtype=t, device=self.dev) for k, t in
+               (("result", torch.uint8), ("status", torch.uint8), ("table", torch.int32),
+                ("block", torch.int32), ("entry", torch.int32))}
+        out["val_pos"] = torch.empty(n + 1, dtype=torch.int64, device=self.dev)
+        self.ctx.lsm_get_keys_ptrs(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(),
+                                   self.n_tables, self.level_first.ctypes.data, self.n_levels,
+                                   q.data_ptr(), qp.data_ptr(), n, out["result"].data_ptr(),
+                                   out["status"].data_ptr(), out["table"].data_ptr(),
+                                   out["block"].data_ptr(), out["entry"].data_ptr(),
+                                   out["val_pos"].data_ptr(),
+                                   torch.cuda.current_stream(self.dev).cuda_stream)
+        out["n"] = n
+        out["_keys"] = (q, qp)      # alive until the stream has run the walk
+        return out
+
+    def values(self, w: dict, total: int) -> torch.Tensor:
+        """tpz_lsm_get_values on the current stream: the packed values (uint8, `total` bytes)."""
+        vals = torch.empty(max(total, 1), dtype=torch.uint8, device=self.dev)
+        self.ctx.lsm_get_values_ptrs(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(),
+                                     self.n_tables, w["n"], w["result"].data_ptr(),
+                                     w["table"].data_ptr(), w["block"].data_ptr(),
+                                     w["entry"].data_ptr(), w["val_pos"].data_ptr(),
+                                     vals.data_ptr(), total,
+                                     torch.cuda.current_stream(self.dev).cuda_stream)
+        return vals[:total]
+
+    def scan_ranges(self, ranges: list, limit: int) -> dict:
+        """tpz_lsm_scan_ranges on the current stream: DeviceLevels.scan_ranges' outputs."""
+        n = len(ranges)
+        lo = [_bound(r[0], True) for r in ranges]
+        hi = [_bound(r[1], False) for r in ranges]
+        dev = self.dev
+        cols = []
+        for side in (lo, hi):
+            buf, pos = _pack([k for _, k in side])
+            cols += [torch.from_numpy(buf.copy()).to(dev), torch.from_numpy(pos).to(dev),
+                     torch.from_numpy(np.array([k for k, _ in side] or [0], np.uint8)).to(dev)]
+        out = {k: torch.empty(max(n, 1), dtype=torch.uint8, device=dev) for k in ("result", "status")}
+        out["where"] = torch.empty((max(n, 1), 3), dtype=torch.int32, device=dev)
+        for k in ("hit_table", "hit_block", "hit_entry"):
+            out[k] = torch.empty(max(n * limit, 1), dtype=torch.int32, device=dev)
+        for k in ("first", "key_first", "val_first"):
+            out[k] = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        out["info"] = torch.empty(3, dtype=torch.int64, device=dev)
+        self.ctx.lsm_scan_ranges_ptrs(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(),
+                                      self.n_tables, self.level_first.ctypes.data, self.n_levels,
+                                      *(c.data_ptr() for c in cols), n, limit,
+                                      *(out[k].data_ptr() for k in
+                                        ("result", "status", "where", "hit_table", "hit_block",
+                                         "hit_entry", "first", "key_first", "val_first", "info")),
+                                      torch.cuda.current_stream(dev).cuda_stream)
+        out["n"], out["limit"] = n, limit
+        out["_bounds"] = cols        # alive until the stream has run the scan
+        return out
+
+    def scan_entries(self, s: dict, totals) -> dict:
+        """tpz_lsm_scan_entries on the current stream over scan_ranges' outputs."""
+        n_ent, kbytes, vbytes = (int(x) for x in totals)
+        dev = self.dev
+        out = {"kpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
+               "vpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
+               "keys": torch.empty(max(kbytes, 1), dtype=torch.uint8, device=dev),
+               "values": torch.empty(max(vbytes, 1), dtype=torch.uint8, device=dev)}
+        self.ctx.lsm_scan_entries_ptrs(self.d_runs.data_ptr(), self.n_runs,
+                                       self.d_tables.data_ptr(), self.n_tables, s["n"], s["limit"],
+                                       s["hit_table"].data_ptr(), s["hit_block"].data_ptr(),
+                                       s["hit_entry"].data_ptr(), s["first"].data_ptr(),
+                                       out["keys"].data_ptr(), kbytes, out["kpos"].data_ptr(),
+                                       out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
+                                       torch.cuda.current_stream(dev).cuda_stream)
+        out["keys"], out["values"] = out["keys"][:kbytes], out["values"][:vbytes]
+        return out
+
+    def scan(self, lower=None, upper=None, page: int = 256) -> ScanIterator:
+        """lsm_storage.rs:335-374: is_valid() / key() / value() / next(). A page that reported
+        MORE is continued with ("after", its last key) over the same runs."""
+        return ScanIterator(self, lower, upper, page)
+
+    def error(self, status: int, table: int, block: int, entry: int) -> Exception:
+        if table == GET_NONE:                        # assert!(!key.is_empty()) (lsm_storage.rs:199)
+            return ReferencePanic("key cannot be empty")
+        return super().error(status, table, block, entry)
