@@ -32,7 +32,8 @@
 //  one) source segment(s) covering it, then one coalesced dwordx4 store (1 KiB per wave
 //  instruction). A regular block (every entry one key length and one value length, both >= 16,
 //  back to back) skips the table and the map on the slotted wave path: its ends and the copy's
-//  chunk -> entry index are closed forms of (n, KL, VL) (decode_block, copy_crc_piped<.., REG>).
+//  chunk -> entry index are closed forms of (n, KL, VL) (decode_block, copy_crc_piped<.., REG>);
+//  a wave computes that index once per (n, KL, VL) and keeps it, packed, in its idle entry table.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -96,6 +97,10 @@ constexpr int kWaveMapLen = 288;                    // >= (kWaveMaxLen + 2) / 16
 constexpr int kSlotBytes = kGuard + kWinBytes + 32 + kWaveTabSlots * 4 + 2 * kWaveMapLen;
 static_assert(kSlotBytes % 16 == 0 && kWaveMapLen % 8 == 0, "slot alignment");
 static_assert(2 * kWaveMaxN + 1 <= (u32)kWaveTabSlots, "entry table");
+// (the regular path's copy index, 16 bytes per lane, lies at the head of the entry table, in the
+// timing build with the short table in the map too: a regular block uses neither, and the
+// general parse, which writes both, invalidates it)
+static_assert(kWaveTabSlots * 4 + 2 * kWaveMapLen >= kWave * 16, "index cache");
 constexpr int kWaveLds = kWaveTabBytes + kWavesPerWG * kSlotBytes;
 static_assert(kWaveLds <= 163840, "wave path LDS");
 
@@ -1117,8 +1122,11 @@ struct RegGeom {
 // divisor and dividend). y and m are below 2^24: the product is two 24-bit multiplies.
 constexpr u32 kRegShift = 26;
 __device__ __forceinline__ u32 reg_recip(u32 d) {
-  u32 m = (u32)(__builtin_amdgcn_rcpf((float)d) * (float)(1u << kRegShift)) + 2u;
-  asm volatile("" : "+v"(m));   // (finished here, once per block, not behind the readfirstlane)
+  float f = (float)d;
+  asm volatile("" : "+v"(f));   // (the reciprocal stays where it is asked for: not hoisted above
+                                // the index cache's key compare, onto the path of a hit)
+  u32 m = (u32)(__builtin_amdgcn_rcpf(f) * (float)(1u << kRegShift)) + 2u;
+  asm volatile("" : "+v"(m));   // (finished here, not behind the readfirstlane)
   return uni(m);
 }
 // (the masks tell the compiler that the factors fit 24 bits: full-rate v_mul_u32_u24 /
@@ -1129,14 +1137,93 @@ __device__ __forceinline__ u32 reg_div(u32 y, u32 m) {
   return __builtin_amdgcn_alignbit((u32)(p >> 32), (u32)p, kRegShift) & 0x3FFu;
 }
 
-// REG: the block is regular (G) and the windows' j, e0, d0, d1, cross come from reg_index instead
-// of the map, the prefix max and the entry table (col, map, nk are not read).
+// Chunk c of a regular block at x0 = 16 c lies in key j = x0 / KL (x0 < n KL: the values start on
+// a chunk boundary, so no chunk holds both) or in value j = (x0 - vs) / VL. With L that entry's
+// length, base the region's start in the stream (0 or vs) and r = x0 - base - j L the chunk's
+// first byte within the entry, the source is db + j S + 2 (+ 2 + KL) + r, so d0 = source - x0 =
+// C + j T with T = S - L and C uniform; the entry ends at e0 = base + (j + 1) L, and the next
+// one's bytes lie T further on (d1 = d0 + T). A chunk crosses at most one boundary (L >= 16).
+// The last key's chunk crosses into the key/value gap (unspecified bytes): it takes what the
+// general path reads there, the bytes before value 0 (gap: where those lie from the chunk's
+// own source). The last value has no successor (e0 out of reach).
+struct RegForm {
+  u32 n, KL, VL, kc, vs, S, mk, mv;
+  int gap;
+  __device__ __forceinline__ RegForm(u32 n_, u32 KL_, u32 VL_) : n(n_), KL(KL_), VL(VL_) {
+    kc = n * KL, vs = (kc + 15) & ~15u, S = 4 + KL + VL;
+    mk = reg_recip(KL), mv = reg_recip(VL);
+    gap = (int)(2 + KL) - (int)vs - (int)((n - 1) * (4 + VL));
+  }
+  // (db: the entries region in the window; 0 gives the offsets the index cache holds)
+  __device__ __forceinline__ void entry(u32 x0, u32 db, bool isk, u32& e0, int& d0, int& d1) const {
+    const u32 L = isk ? KL : VL, base = isk ? 0u : vs, T = S - L;
+    const u32 j = reg_div(x0 - base, isk ? mk : mv);
+    const bool last = j + 1 == n;
+    e0 = (!isk && last) ? 0xFFFFu : base + mul24(j + 1, L);     // (j < 2^10, L and T < 2^13)
+    d0 = (int)((isk ? db + 2 : db + 4 + KL - vs) + mul24(j, T));
+    d1 = d0 + ((isk && last) ? gap : (int)T);
+  }
+  __device__ __forceinline__ void index(u32 w, u32 lane, u32 db, u32& e0, int& d0, int& d1) const {
+    const u32 x0 = 16 * (64 * w + lane);
+    // (a window wholly in the keys or wholly in the values: scalar selects)
+    if (1024 * (w + 1) <= kc) entry(x0, db, true, e0, d0, d1);
+    else if (1024 * w >= vs) entry(x0, db, false, e0, d0, d1);
+    else entry(x0, db, x0 < kc, e0, d0, d1);
+  }
+};
+// The index cache: what the gathers and the merge of chunk c take, relative to db,
+// in one word: bits 0-12 the chunk's source x0 + d0 - db, bits 13-25 its successor's x0 + d1 - db
+// + kRegBias (a crossing chunk's only, else 0), bits 26-30 m = e0 - x0, the bytes before the
+// boundary (1..15), or 16: no crossing; bit 31: no chunk c (it reads the guard). The block is at
+// most 4336 bytes and every source lies in it (tests/test_regular_cache_pack.py walks the shapes).
+constexpr u32 kRegBias = 16, kRegNoChunk = 0x80000000u | (16u << 26);
+__device__ __forceinline__ u32 reg_pack(const RegForm& R, u32 w, u32 lane, u32 nch) {
+  const u32 c = 64 * w + lane, x0 = 16 * c;
+  u32 e0;
+  int d0, d1;
+  R.entry(x0, 0u, x0 < R.kc, e0, d0, d1);     // (once per geometry: per-lane selects will do)
+  const bool cross = e0 < x0 + 16;
+  const u32 word = ((x0 + (u32)d0) & 0x1FFFu) |
+                   (cross ? (((x0 + (u32)d1 + kRegBias) & 0x1FFFu) << 13) | ((e0 - x0) << 26) : 16u << 26);
+  return c < nch ? word : kRegNoChunk;
+}
+// The geometry whose index the wave's cache holds, in one word (one register across the block
+// loop: with two the loop's SGPR spills went from 33 to 347). A regular block has n (6 + KL + VL) <=
+// 4329, so n >= 2 leaves KL, VL < 4096: n << 24 | VL << 12 | KL with n <= 113; n = 1 sets bit 31
+// and takes 13 bits for each. kRegNone: no index (a wave's first block, and after a parse that
+// wrote the entry table).
+constexpr u32 kRegNone = 0u;
+__device__ __forceinline__ u32 reg_key(u32 n, u32 KL, u32 VL) {
+  return n == 1 ? 0x80000000u | VL << 13 | KL : n << 24 | VL << 12 | KL;
+}
+// (the key and the index words exist in the slotted wave kernel only: the other instances of
+// decode_block and of the block loop compile to what they were)
+template <bool ON>
+struct RegKeyVar {
+  u32 key = kRegNone;
+  __device__ __forceinline__ u32* ptr() { return &key; }
+};
+template <>
+struct RegKeyVar<false> {
+  __device__ __forceinline__ u32* ptr() { return nullptr; }
+};
+template <bool ON>
+struct RegWords {
+  u32x4v v;
+};
+template <>
+struct RegWords<false> {};
+
+// REG: the block is regular (G) and the windows' sources, successors and crossings come from the
+// packed index rix (reg_pack: the wave's cache or built for this block) instead of the map, the
+// prefix max and the entry table (col, map, nk are not read).
 template <bool FLAT, u32 K3, bool REG = false>
 __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& col,
                                               const uint16_t* map, u32 nk, u32 tot, uint8_t* dst,
                                               const FlatOut& D, const uint8_t* win, int pb, u32 Pa,
                                               const Out& o, PendingCrc& pd, u32 k3n = K3,
-                                              const RegGeom G = RegGeom{0u, 0u, 0u, 0u}) {
+                                              const RegGeom G = RegGeom{0u, 0u, 0u, 0u},
+                                              const u32x4v rix = u32x4v{0u, 0u, 0u, 0u}) {
   static_assert(!REG || (K3 == 0 && !FLAT), "the regular copy: slotted, no short keys");
   // (k3n <= K3, uniform: the windows that hold short keys; the others take the plain rule)
   const u32 lane = lane_id();
@@ -1158,42 +1245,24 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   };
   PWin W[4];
   PWin3 W3;
-  // REG: chunk c at x0 = 16 c lies in key j = x0 / KL (x0 < n KL: the values start on a chunk
-  // boundary, so no chunk holds both) or in value j = (x0 - vs) / VL. With L that entry's length,
-  // base the region's start in the stream (0 or vs) and r = x0 - base - j L the chunk's first
-  // byte within the entry, the source is db + j S + 2 (+ 2 + KL) + r, so d0 = source - x0 =
-  // C + j T with T = S - L and C uniform; the entry ends at e0 = base + (j + 1) L, and the next
-  // one's bytes lie T further on (d1 = d0 + T). A chunk crosses at most one boundary (L >= 16).
-  // The last key's chunk crosses into the key/value gap (unspecified bytes): it takes what the
-  // general path reads there, the bytes before value 0 (r_gap: where those lie from the chunk's
-  // own source). The last value has no successor (e0 out of reach).
-  const u32 r_kc = G.n * G.KL, r_vs = (r_kc + 15) & ~15u, r_S = 4 + G.KL + G.VL;
-  const u32 r_mk = REG ? reg_recip(G.KL) : 0u, r_mv = REG ? reg_recip(G.VL) : 0u;
-  const int r_gap = (int)(2 + G.KL) - (int)r_vs - (int)((G.n - 1) * (4 + G.VL));
-  auto reg_entry = [&](PWin& P, u32 x0, bool isk) {
-    const u32 L = isk ? G.KL : G.VL, base = isk ? 0u : r_vs, T = r_S - L;
-    const u32 j = reg_div(x0 - base, isk ? r_mk : r_mv);
-    const bool last = j + 1 == G.n;
-    P.j = 0;
-    P.e0 = (!isk && last) ? 0xFFFFu : base + mul24(j + 1, L);     // (j < 2^10, L and T < 2^13)
-    P.d0 = (int)((isk ? G.db + 2 : G.db + 4 + G.KL - r_vs) + mul24(j, T));
-    P.d1 = P.d0 + ((isk && last) ? r_gap : (int)T);
-  };
-  auto reg_index = [&](PWin& P, u32 w) {
-    const u32 x0 = 16 * (64 * w + lane);
-    // (a window wholly in the keys or wholly in the values: scalar selects)
-    if (1024 * (w + 1) <= r_kc) reg_entry(P, x0, true);
-    else if (1024 * w >= r_vs) reg_entry(P, x0, false);
-    else reg_entry(P, x0, x0 < r_kc);
-    // (computed here, in stage B, not sunk between a window's store and the next one's gathers)
+  // REG: a window's PWin holds d0, d1 = the LDS offsets its two gathers read (the guard where
+  // there is no chunk or no crossing) and e0 = m, the bytes before the boundary. One add per
+  // address: db changes with every block and is not in the index.
+  auto reg_unpack = [&](PWin& P, u32 word) {
+    P.e0 = (word >> 26) & 31u;
+    P.d0 = (int)word < 0 ? -kGuard : (int)(G.db + (word & 0x1FFFu));
+    P.d1 = P.e0 < 16 ? (int)(G.db - kRegBias + ((word >> 13) & 0x1FFFu)) : -kGuard;
+    // (unpacked here, in stage B, not sunk between a window's store and the next one's gathers)
     asm volatile("" : "+v"(P.e0), "+v"(P.d0), "+v"(P.d1));
   };
   // A: map reads, CRC data of step 0
+  if constexpr (!REG) {
 #pragma unroll
-  for (int w = 0; w < 4; w++) {
-    const u32 c = 64 * w + lane;
-    W[w].act = c < F.nch;
-    if (!REG) W[w].m = map[min(c, (u32)kWaveMapLen - 1)];
+    for (int w = 0; w < 4; w++) {
+      const u32 c = 64 * w + lane;
+      W[w].act = c < F.nch;
+      W[w].m = map[min(c, (u32)kWaveMapLen - 1)];
+    }
   }
   u32x4v dA = dread(0);
   // the pending combine: level 0, and shift_k(~stored), the value R is compared with
@@ -1202,12 +1271,14 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   const u32 want = crc_shift_small(tab, ~pd.stored, pd.k);
   TPZ_SB();
   // B: prefix max per window (independent DPP chains), carries, entries j and j + 1
-  //    (REG: the closed form, no LDS read)
+  //    (REG: the packed index, unpacked)
   u32 cw[5];
   cw[0] = 0;
   if (REG) {
-#pragma unroll
-    for (int w = 0; w < 4; w++) reg_index(W[w], (u32)w);
+    reg_unpack(W[0], rix.x);
+    reg_unpack(W[1], rix.y);
+    reg_unpack(W[2], rix.z);
+    reg_unpack(W[3], rix.w);
   } else {
 #pragma unroll
     for (int w = 0; w < 4; w++) W[w].j = wave_scan_max(W[w].act ? W[w].m : 0u);
@@ -1231,6 +1302,11 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   TPZ_SB();
   u32 rare = 0;
   auto gissue = [&](PWin& P, u32 w) {
+    if constexpr (REG) {
+      P.ga = gath_issue(win, P.d0);
+      P.gn = gath_issue(win, P.d1);
+      return;
+    }
     const u32 x0 = 16 * (64 * w + lane);
     if (w < K3 && w < k3n) {
       // (window 0's entries j + 2, j + 3 were read with its others; a later window's are read
@@ -1254,6 +1330,13 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   auto finish = [&](PWin& P, u32 w) {
     const u32 c = 64 * w + lane;
     const u32 x0 = 16 * c;
+    if constexpr (REG) {
+      uint4 acc = gath_finish(P.ga, P.d0);
+      const uint4 nx = gath_finish(P.gn, P.d1);
+      if (P.e0 < 16) acc = merge_at(acc, nx, (int)P.e0);   // (no mask held across the stages)
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, acc), F.out, x0, 0, 0);
+      return;
+    }
     // (no rare path outside a K3 window 0: the other windows hold values of 16 bytes or more,
     // so no two segments end in one chunk and no chunk meets three segments)
     const bool rw = w < K3 && w < k3n && (rare & (1u << w));
@@ -1313,9 +1396,16 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   TPZ_SB();
   crc = look_xor(LK);
   if (nw > 4) {
-    if (REG) {              // the fifth window by the same closed form
-      W[0].act = 256 + lane < F.nch;
-      reg_index(W[0], 4u);
+    if (REG) {              // the fifth window by the closed form (rare: not in the index)
+      const RegForm R(G.n, G.KL, G.VL);
+      const u32 x0 = 16 * (256 + lane);
+      u32 e0;
+      int d0, d1;
+      R.index(4u, lane, G.db, e0, d0, d1);
+      const bool act = 256 + lane < F.nch, cross = act && e0 < x0 + 16;
+      W[0].e0 = cross ? e0 - x0 : 16u;
+      W[0].d0 = act ? (int)x0 + d0 : -kGuard;
+      W[0].d1 = cross ? (int)x0 + d1 : -kGuard;
       gissue(W[0], 4u);
       finish(W[0], 4u);
     } else {
@@ -1355,7 +1445,7 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
                                              MapT* map, u32 a0, u32 len, u32 b, u64 ext_b,
                                              const Out& o, u32 kshift, Stamps& S, PendingCrc& pd,
                                              u64 kf = 0, u64 vf = 0, u64 ef = 0,
-                                             const Out* o_lds = nullptr) {
+                                             const Out* o_lds = nullptr, u32* rk = nullptr) {
   const u32 lane = lane_id();
   // the header reads are issued together (one LDS round trip); the checks keep the reference's
   // order
@@ -1376,6 +1466,7 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
     e_ok = len >= 7 && lane < n && Pn >= 2 + 2 * n && e_off + 2 <= Pn - 2 - 2 * n;
     e_kl = lds_be16(win, e_ok ? db0 + e_off : a0);
   }
+  RegWords<!BIG && !FLAT> rix;   // the block's packed copy index (slotted wave path, regular)
   // The previous block's combine: after a short-segment block it runs here, behind this block's
   // header reads (whose round trips it overlaps); otherwise this block's copy runs it level by
   // level between its own steps (copy_crc_piped / copy_crc_fused), and every other exit of this
@@ -1457,16 +1548,36 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
         }
         TPZ_STAMP(S, 2);
         TPZ_STAMP(S, 3);
+        // The copy index depends on (n, KL, VL) alone (db is added where it is used): a block
+        // with the geometry of the wave's last regular block takes the wave's cached words. Any
+        // other builds the index by the closed form, caches it and goes on from its own words.
+        // (The cached words, lane l's four windows at the head of the entry table, are read here,
+        // whatever they hold, and used only on a hit: the read's round trip overlaps the ends
+        // store and crc_prepare. Read with the header, before the test, the 4k copy ran 0.1-0.4 %
+        // faster and zipf batches, which never use it, 0.1-0.5 % slower: profiles/regcache/.)
+        const u32 key = reg_key(n, KL, VL);
+        rix.v = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const uint8_t*>(col.t) + 16 * lane);
+        if (*rk != key) {
+          const RegForm R(n, KL, VL);
+          const u32 nch = (vs + vc + 15) >> 4;
+          // (a loop, not unrolled, and read back: a miss is rare and its code stays small)
+#pragma nounroll
+          for (u32 w = 0; w < 4; w++) col.t[4 * lane + w] = reg_pack(R, w, lane, nch);
+          rix.v = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const uint8_t*>(col.t) + 16 * lane);
+          *rk = key;
+        }
         __builtin_amdgcn_wave_barrier();
         const u32 k = crc_prepare(win, a0, P);
         fin.on = false;     // the previous block's combine runs in the copy, before pd is reused
         const u32 lc = copy_crc_piped<false, 0u, true>(
             tab, *reinterpret_cast<const ColSmall*>(&col), reinterpret_cast<const uint16_t*>(map),
             2 * n, vs + vc, o.data + slot_base(ext_b, b), fo, win, pb, P + k, o, pd, 0u,
-            RegGeom{n, KL, VL, db});
+            RegGeom{n, KL, VL, db}, rix.v);
         pd = PendingCrc{1u, b, st, cnt, stored, k, lc, 0u};   // combined during the next block
         return;
       }
+      // the general parse writes the entry table over the cached index
+      *rk = kRegNone;
     }
     {
       // clear the chunk map up to the largest chunk index a block that fits its slot can
@@ -2041,6 +2152,7 @@ void decode_wave_kernel(Params p) {
     }
   };
   PendingCrc pd{0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  RegKeyVar<!FLAT> rk;                  // (uniform) the geometry of the wave's cached copy index
 #ifndef TPZ_ABL_NOPF
   issue(b, 0, s_cur, e_cur);
 #endif
@@ -2092,7 +2204,7 @@ void decode_wave_kernel(Params p) {
 #endif
       decode_block<ColSmall, uint16_t, kWaveMapLen, false, FLAT>(tab, win, col, map, (u32)(s & 15u),
                                                            len64, bdec, s, p.out, kshift, S, pd, kf, vf,
-                                                           ef, &out_lds);
+                                                           ef, &out_lds, rk.ptr());
     }                                // (long blocks went to their worklist in triage_group)
     __builtin_amdgcn_wave_barrier();
     TPZ_STAMP(S, 5);
