@@ -409,7 +409,8 @@ class Context:
     def decode_host_ptrs(self, h_src: int, h_ext: int, n_blocks: int, cols: HostColumns,
                          chunk_blocks: int = 0) -> int:
         """tpz_decode_blocks_host (blocks in host memory; H2D, decode, D2H inside the library).
-        Returns the tpz_err (SUCCESS, or ERR_NOMEM when ends/spill capacity was short)."""
+        Returns the tpz_err (SUCCESS, or ERR_NOMEM when the ends, spill or data capacity was
+        short)."""
         rc = lib().tpz_decode_blocks_host(self.handle, C.c_void_p(h_src), C.c_void_p(h_ext),
                                           n_blocks, C.byref(cols), chunk_blocks)
         if rc not in (SUCCESS, ERR_NOMEM):

@@ -28,6 +28,15 @@
 // out of bounds) and an overflow flag; the host grows the buffers and runs the chunk again when
 // it reads the chunk's metadata. No whole-batch host sync.
 //
+// Rejected streams. A block whose codec step fails keeps a 1-byte stub in the decoded layout (its
+// tag-0 form). The sizes pass knows an lz4 Err (it walks the stream) but gives a snappy block its
+// preamble's length, and only the codec step finds that stream broken. A chunk that reports such
+// a block is laid out again when the host reads its metadata: the sizes of its rejected blocks
+// (kept in the slot's d_reject, apart from the codec status that every run rewrites) are set to 1
+// (stub_sizes_kernel) and the chunk runs again, and so does the next chunk, already issued from
+// a decoded base that has now moved. Batches without a rejected snappy stream (all
+// that the reference's writer produces) never take this path.
+//
 // Three streams and three buffer slots, so that the two copy directions run at once:
 //   up:    H2D of chunk k's blocks and extents (after chunk k-3's downloads freed its slot)
 //   comp:  the codec step, decode, the entry prefix (count_prefix_kernel), D2H of the per-block
@@ -107,9 +116,11 @@ struct Slot {
   Buf d_src, d_ext, d_data, d_ends, d_count, d_status, d_crc, d_spill, d_spill_off, d_used,
       d_first, d_dense;
   Buf d_size, d_dext, d_gext, d_dst, d_cstat, d_meta;          // the codec step
+  Buf d_reject;        // d_cstat of the run that found the chunk's rejected blocks (stub)
   Buf h_ext, h_first, h_count, h_status, h_crc, h_spill_off, h_used, h_gext, h_meta;
   uint32_t lo = 0, hi = 0, k = 0;
   uint64_t base = 0;   // host byte of device byte 0 (a multiple of 384)
+  bool stub = false;   // lay the chunk out with 1-byte stubs for the blocks d_reject names
   Slot() {
     h_ext.host = h_first.host = h_count.host = h_status.host = h_crc.host = h_spill_off.host =
         h_used.host = h_gext.host = h_meta.host = true;
@@ -172,6 +183,14 @@ __global__ __launch_bounds__(1024) void chunk_extents_kernel(const uint64_t* siz
     meta->need_ends = need_ends;
     meta->overflow = over ? 1u : 0u;
   }
+}
+
+// The blocks the codec step rejected take 1 byte of the decoded layout. `reject` is the codec
+// status of the run that found them, not of the chunk's latest run: a run whose buffers
+// overflowed has empty extents and rejects every codec block.
+__global__ void stub_sizes_kernel(const uint8_t* reject, uint64_t* size, uint32_t m) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m && reject[i] != TPZ_BLOCK_OK) size[i] = 1;
 }
 
 // A block whose codec step failed reports the codec's status (its stub decodes as BAD_TAG).
@@ -436,6 +455,11 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
     if (codec) {
       tpz_err r = tpz_decompressed_sizes(ctx, &bc, S.d_size.as<uint64_t>(), P->comp);
       if (r != TPZ_SUCCESS) return r;
+      if (S.stub) {
+        hipLaunchKernelGGL(stub_sizes_kernel, dim3((m + 255) / 256), dim3(256), 0, P->comp,
+                           S.d_reject.as<uint8_t>(), S.d_size.as<uint64_t>(), m);
+        PIPE_HIP(hipGetLastError());
+      }
       hipLaunchKernelGGL(chunk_extents_kernel, dim3(1), dim3(1024), 0, P->comp,
                          S.d_size.as<uint64_t>(), m, P->d_chunk_base.as<uint64_t>(), S.k,
                          (uint64_t)S.d_dst.n, (uint64_t)S.d_data.n, (uint64_t)(S.d_ends.n / 4),
@@ -480,6 +504,7 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
       PIPE_HIP(hipEventSynchronize(S.ev_up));
     }
     S.used = true;
+    S.stub = false;
     S.k = k;
     S.lo = k * cb;
     S.hi = std::min(n, S.lo + cb);
@@ -496,11 +521,22 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
   };
 
   uint64_t g_first = 0, g_spill = 0;
+  uint64_t g_dend = 0;    // codec batches: decoded bytes of the chunks finished so far
+  bool relaid = false;    // finish() laid its chunk out again: the next chunk's base moved
   bool short_ends = false, short_spill = false, short_data = false, short_plain = false;
   auto finish = [&](Slot& S) -> tpz_err {
     PIPE_HIP(hipEventSynchronize(S.ev));
     const uint32_t m = S.hi - S.lo;
-    for (int redo = 0; redo < 4; redo++) {
+    // a rejected block whose decoded range is not the 1-byte stub (a snappy stream that broke
+    // after a valid preamble, or whose preamble is invalid)
+    auto wants_stubs = [&]() {
+      const uint8_t* st = S.h_status.as<uint8_t>();
+      const uint64_t* gx = S.h_gext.as<uint64_t>();
+      for (uint32_t j = 0; j < m; j++)
+        if (st[j] == TPZ_BLOCK_CODEC_ERROR && gx[j + 1] - gx[j] != 1) return true;
+      return false;
+    };
+    for (int redo = 0; redo < 5; redo++) {
       bool again = false;
       if (codec) {
         const ChunkMeta& cm = *S.h_meta.as<ChunkMeta>();
@@ -511,6 +547,15 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
           PIPE_HIP(S.d_data.ensure(cm.need_data + (cm.need_data >> 2)));
           PIPE_HIP(S.d_ends.ensure(4 * (cm.need_ends + (cm.need_ends >> 2))));
           PIPE_HIP(S.d_dense.ensure(4 * (cm.need_ends + (cm.need_ends >> 2))));
+          again = true;
+        } else if (!S.stub && wants_stubs()) {  // lay the chunk out again, its rejects at 1 byte
+          // (this run did not overflow, so its codec status names exactly the rejected blocks;
+          //  a stub run may overflow by the bytes its empty ranges gain, and is then run again
+          //  from this copy)
+          PIPE_HIP(S.d_reject.ensure(m));
+          PIPE_HIP(hipMemcpyAsync(S.d_reject.p, S.d_cstat.p, m, hipMemcpyDeviceToDevice, P->comp));
+          S.stub = true;
+          relaid = true;
           again = true;
         }
       }
@@ -531,7 +576,14 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
     // short, so a caller that grows its buffers on NOMEM and calls again would loop for ever.
     if ((codec && S.h_meta.as<ChunkMeta>()->overflow) || *S.h_used.as<uint64_t>() > S.d_spill.n) {
       return tpz_internal_fail(TPZ_ERR_INTERNAL,
-                               "tpz_decode_blocks_host: chunk buffers still overflow after 4 decodes");
+                               "tpz_decode_blocks_host: chunk buffers still overflow after 5 decodes");
+    }
+    // a consistency check only: the main loop decodes the chunk issued after a laid-out-again
+    // chunk a second time, so every chunk reaches this point decoded from the base the chunks
+    // before it ended at
+    if (codec && S.h_meta.as<ChunkMeta>()->dbase != g_dend) {
+      return tpz_internal_fail(TPZ_ERR_INTERNAL,
+                               "tpz_decode_blocks_host: a chunk was decoded from a stale base");
     }
     const uint64_t used = *S.h_used.as<uint64_t>();
     const uint64_t* first = S.h_first.as<uint64_t>();
@@ -540,8 +592,10 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
     const uint64_t* gx = codec ? S.h_gext.as<uint64_t>() : nullptr;
     const uint64_t e_lo = codec ? gx[0] : h_ext[S.lo], e_hi = codec ? gx[m] : h_ext[S.hi];
     const uint64_t dbase = codec ? S.h_meta.as<ChunkMeta>()->dbase384 : S.base;
-    if (codec)
+    if (codec) {
       for (uint32_t i = 0; i <= m; i++) o->h_dext[S.lo + i] = gx[i];
+      g_dend = e_hi;
+    }
     PIPE_HIP(hipStreamWaitEvent(P->down, S.ev, 0));
     if (verify) {
       // the decoded (Uncompress) bytes of a codec chunk: device byte e - dbase holds batch byte e
@@ -629,7 +683,11 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
       if (r != TPZ_SUCCESS) return r;
     }
     if (k >= 1) {
+      relaid = false;
       tpz_err r = finish(slot[(k - 1) % kSlots]);
+      if (r != TPZ_SUCCESS) return r;
+      // chunk k was issued from the decoded base chunk k-1 first reported: decode it again
+      if (relaid && k < n_chunks) r = decode_chunk(slot[k % kSlots]);
       if (r != TPZ_SUCCESS) return r;
     }
   }
@@ -639,5 +697,8 @@ static tpz_err host_pipeline(tpz_ctx* ctx, const uint8_t* h_src, const uint64_t*
   // every chunk decoded to completion (tpz_decode_check: no timed-out tail wait on comp)
   const tpz_err chk = tpz_decode_check(ctx, P->comp);
   if (chk != TPZ_SUCCESS) return chk;
+  // h_data holds tpz_data_capacity of the decoded bytes (the size a caller derives from h_dext[n]),
+  // though the copies above end at the last slot's end, 128 bytes before it
+  if (!verify && data_cap < tpz_data_capacity(codec ? g_dend : h_ext[n], n)) short_data = true;
   return (short_ends || short_spill || short_data || short_plain) ? TPZ_ERR_NOMEM : TPZ_SUCCESS;
 }
