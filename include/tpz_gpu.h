@@ -23,6 +23,9 @@
  *   tpz_encode_blocks       block_build (src/table/builder.rs:49-85) over entries in HBM
  *   tpz_merge_runs          MergeIterator over one SsTableIterator per input table, as sub_compact
  *                           drives it (src/iterators/merge_iterator.rs:41-106, src/level.rs:178-222)
+ *   tpz_mem_build +         a memtable run from entries in arrival order: MemTable::open's replay
+ *   tpz_wal_index +         (src/mem_table.rs:119-143, over WalIterator, src/wal/iterator.rs) and
+ *   tpz_wal_entries         do_mem_put's versions (:155-196), with MemTable::size()
  *   tpz_get_keys +          LevelController::get (src/level.rs:427-465) for a batch of keys over
  *   tpz_get_values          tables resident in HBM: the walk over L0 and the levels, then the values
  *   tpz_entries_bound +     do_compact around the merge (src/level.rs:133-222): sub_compact's key
@@ -80,7 +83,9 @@ extern "C" {
  *      runs as a resident input (tpz_mem_run, tpz_mem_prefix, TPZ_MEM_MAX_RUNS, TPZ_HIT_MEM) and
  *      LsmStorage::get and LsmStorage::scan over runs plus tables (tpz_lsm_get_keys,
  *      tpz_lsm_get_values, tpz_lsm_scan_ranges, tpz_lsm_scan_entries); a consumer tests
- *      TPZ_HAS_MEM
+ *      TPZ_HAS_MEM. Same ABI, additive: building a memtable run on the device from a write batch
+ *      or a WAL image (tpz_mem_build, tpz_wal_index, tpz_wal_entries, TPZ_MEM_REPLAY / TPZ_MEM_PUT,
+ *      TPZ_WAL_*); a consumer tests TPZ_HAS_MEM_BUILD
  * A consumer compiled against one header checks tpz_abi_version() == TPZ_ABI_VERSION. */
 #define TPZ_ABI_VERSION 8
 int tpz_abi_version(void);
@@ -967,6 +972,98 @@ tpz_err tpz_lsm_scan_entries(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n
                              const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
                              uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
                              void* stream);
+
+/* ---- building a memtable run: write batches and WAL images ----------------------------------
+ * The stage in front of the runs above: entries in ARRIVAL order (a write batch, or the records
+ * of a WAL image) become a run (keys strictly increasing, one entry per distinct key) with the
+ * reference's replacement rules and its MemTable::size(), ready for tpz_mem_run. Additive within
+ * ABI 8: new symbols and constants only (TPZ_HAS_MEM_BUILD tells a consumer the header has them).
+ *
+ * tpz_mem_build. `entries` is a tpz_entries whose keys are in arrival order, not sorted. Two rules
+ * (src/mem_table.rs), chosen by `mode`:
+ *   TPZ_MEM_REPLAY  MemTable::open (:119-143) over WalIterator (src/wal/iterator.rs). Records are
+ *     read while is_valid() (:125; iterator.rs:30-32: the key is non-empty): the FIRST entry with
+ *     an empty key ends the replay and it and every entry after it are ignored. map.insert (:129)
+ *     replaces: the LAST entry of a key wins. size (:128) = the sum of klen + vlen over every
+ *     entry read, replaced ones included. d_version is ignored.
+ *   TPZ_MEM_PUT     MemTable::put / put_entries -> do_mem_put (:155-196). d_version: n u64 in
+ *     device memory, entry i's WAL append version (all entries of one put_entries batch share
+ *     one, :162-165), non-decreasing in arrival order (a precondition; it suffices that the
+ *     entries of each key have non-decreasing versions, which is what lets a built run's own
+ *     d_out_version column stand in front of a later batch). compare_insert(.., |x|
+ *     x.version < version) (:179-181) replaces only on a strictly greater version: the winner of
+ *     a key is the FIRST entry, in arrival order, among those with the key's highest version
+ *     (inside one batch the first duplicate wins, where replaying that batch's WAL lets the last
+ *     win: the reference's behaviour, kept). An empty key is an ordinary key (MemTable does not
+ *     check it). size: compare_insert returns the entry the map holds afterwards, and the update
+ *     (:185-195) runs when that entry's version equals this entry's: for the entry that inserted
+ *     or replaced, and also for a later entry of the same key and version, which was turned away.
+ *     With h = the entry the map held before entry e arrived (the first entry of e's version if
+ *     that is not e itself, else the first entry of the key's previous version):
+ *       no h:                  size += klen + vlen
+ *       vlen >= vlen_h (:189): size += vlen - vlen_h
+ *       otherwise (:193):      size -= old_size - klen + vlen, which is vlen_h + vlen (the
+ *                              reference's operator precedence, kept)
+ *     The sum wraps as usize does.
+ * Outputs: d_out_keys / d_out_vals (16-byte aligned, capacities entries->key_bytes / val_bytes),
+ * d_out_kpos / d_out_vpos (n + 1 u64 each; [n_out] = the byte totals): the winners in Rust's [u8]
+ * order (bytewise, unsigned, a proper prefix first) with their values; empty values (tombstones)
+ * are kept. Optional, NULL to skip: d_out_prefix (n u64: tpz_mem_prefix of the output keys, so the
+ * result is a tpz_mem_run without a second call), d_src_entry (n u32: the input entry each output
+ * entry is), d_out_version (n u64: the winners' versions, 0 under REPLAY as open() stores, :133;
+ * a later batch is applied by building over {this run's entries and versions, then the batch};
+ * size is then the sum of the calls' sizes minus the first output's klen + vlen total, which the
+ * second call counts again as inserts).
+ * d_info, 8 u64: [0] n_out, [1] output key bytes, [2] output value bytes, [3] the first input
+ * entry with an empty key or UINT64_MAX, [4] size, [5] entries consumed (REPLAY: [3] if there is
+ * an empty key, else n; PUT: n), [6], [7] zero.
+ * Asynchronous on `stream`; uses the stream's grow-only workspace: 40 bytes per entry (the prefix,
+ * two id lists, three scan words) plus under 1 % for partial sums and tile partitions.
+ * n_entries == 0 gives all-zero counts ([3] = UINT64_MAX). TPZ_ERR_INVALID_ARG, before any device
+ * work, for null or misaligned pointers, an unknown mode, PUT without d_version, or n_entries ==
+ * 0xFFFFFFFF. Versions that decrease or positions that are not monotone leave the outputs
+ * unspecified but in bounds: every loop is bounded, every id and span clamped, and nothing is
+ * written past the stated capacities.
+ *
+ * tpz_wal_index (host code, no GPU): WalIterator's chain over a WAL image in host memory, a record
+ * being BE u16 klen | key | BE u16 vlen | value (Entry::encode, src/block/builder.rs:72-81;
+ * iterator.rs:34-45). Writes the record starts h_rec[0 .. n] (h_rec[n] = the end of the last
+ * record read; rec_cap = the u64 h_rec holds, TPZ_ERR_NOMEM if n + 1 exceed it); with h_rec NULL
+ * it only counts. It stops after the first empty-key record, as MemTable::open does; that record
+ * is parsed (its value too: next() reads it) and counted. h_info, 4 u64: [0] n, [1] how the walk
+ * ended (TPZ_WAL_END_IMAGE, TPZ_WAL_END_EMPTY_KEY, TPZ_WAL_TRUNCATED), [2] the end of the last
+ * record read, [3] UINT64_MAX, or for TPZ_WAL_TRUNCATED the byte offset of the record at which the
+ * reference panics (get_u16 on fewer than 2 bytes, iterator.rs:39 / :42; a slice past the end,
+ * :40 / :43); the call then returns TPZ_ERR_SIZES, with [0] the records before it. Never reads
+ * outside the image. The chain is serial and has no checksum, so it stays on the host, where the
+ * file arrives anyway.
+ *
+ * tpz_wal_entries (device): d_image (image_bytes in HBM) and d_rec (n_records + 1 record starts,
+ * tpz_wal_index's) become packed key and value columns with d_kpos / d_vpos (n_records + 1 u64
+ * each): a tpz_entries in arrival order for tpz_mem_build(TPZ_MEM_REPLAY). One thread per record
+ * re-reads klen and vlen and checks rec[i] + 4 + klen + vlen == rec[i + 1] inside the image; a
+ * record that fails contributes empty spans. d_info, 4 u64: [0] n_records, [1] key bytes, [2]
+ * value bytes, [3] the first record that fails or UINT64_MAX. d_keys / d_vals: 16-byte aligned,
+ * image_bytes of capacity each suffice and nothing is written past them. Asynchronous on
+ * `stream`. TPZ_ERR_INVALID_ARG for null or misaligned pointers or n_records == 0xFFFFFFFF. */
+#define TPZ_HAS_MEM_BUILD 1
+#define TPZ_MEM_REPLAY 0u
+#define TPZ_MEM_PUT 1u
+#define TPZ_WAL_END_IMAGE 0u
+#define TPZ_WAL_END_EMPTY_KEY 1u
+#define TPZ_WAL_TRUNCATED 2u
+
+tpz_err tpz_mem_build(tpz_ctx* ctx, const tpz_entries* entries, uint32_t mode,
+                      const uint64_t* d_version, uint8_t* d_out_keys, uint64_t* d_out_kpos,
+                      uint8_t* d_out_vals, uint64_t* d_out_vpos, uint64_t* d_out_prefix,
+                      uint32_t* d_src_entry, uint64_t* d_out_version, uint64_t* d_info,
+                      void* stream);
+tpz_err tpz_wal_index(const uint8_t* h_image, uint64_t image_bytes, uint64_t* h_rec,
+                      uint64_t rec_cap, uint64_t* h_info);
+tpz_err tpz_wal_entries(tpz_ctx* ctx, const uint8_t* d_image, uint64_t image_bytes,
+                        const uint64_t* d_rec, uint32_t n_records, uint8_t* d_keys,
+                        uint64_t* d_kpos, uint8_t* d_vals, uint64_t* d_vpos, uint64_t* d_info,
+                        void* stream);
 
 /* ---- a whole compaction task's output tables ----------------------------------------------
  * What do_compact (src/level.rs:133-222) does around the merge and the block loop: the key ranges

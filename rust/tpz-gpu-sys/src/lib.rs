@@ -80,6 +80,18 @@ pub const TPZ_MEM_MAX_RUNS: u32 = 16;
 /// `d_table = TPZ_HIT_MEM | run` for a hit in a memtable run.
 pub const TPZ_HIT_MEM: u32 = 0x80000000;
 
+/// The header declares `tpz_mem_build`, `tpz_wal_index` and `tpz_wal_entries` (additive within
+/// ABI 8): a memtable run built on the device from a write batch or a WAL image.
+pub const TPZ_HAS_MEM_BUILD: u32 = 1;
+/// `tpz_mem_build`'s `mode`: `MemTable::open`'s rule (the last record of a key wins, the first
+/// empty key ends the replay) or `do_mem_put`'s (the first entry of the highest version wins).
+pub const TPZ_MEM_REPLAY: u32 = 0;
+pub const TPZ_MEM_PUT: u32 = 1;
+/// `tpz_wal_index`'s `h_info[1]`: how the walk ended.
+pub const TPZ_WAL_END_IMAGE: u64 = 0;
+pub const TPZ_WAL_END_EMPTY_KEY: u64 = 1;
+pub const TPZ_WAL_TRUNCATED: u64 = 2;
+
 /// `tpz_batch`: blocks (or ranges, or files) back to back in HBM; block i is
 /// `d_src[d_ext[i] .. d_ext[i + 1])`.
 #[repr(C)]
@@ -313,6 +325,17 @@ extern "C" {
                           d_vals: *mut u8, val_cap: u64, stream: *mut c_void) -> TpzErr;
     pub fn tpz_mem_prefix(ctx: *mut TpzCtx, entries: *const TpzEntries, d_prefix: *mut u64,
                           stream: *mut c_void) -> TpzErr;
+    pub fn tpz_mem_build(ctx: *mut TpzCtx, entries: *const TpzEntries, mode: u32,
+                         d_version: *const u64, d_out_keys: *mut u8, d_out_kpos: *mut u64,
+                         d_out_vals: *mut u8, d_out_vpos: *mut u64, d_out_prefix: *mut u64,
+                         d_src_entry: *mut u32, d_out_version: *mut u64, d_info: *mut u64,
+                         stream: *mut c_void) -> TpzErr;
+    pub fn tpz_wal_index(h_image: *const u8, image_bytes: u64, h_rec: *mut u64, rec_cap: u64,
+                         h_info: *mut u64) -> TpzErr;
+    pub fn tpz_wal_entries(ctx: *mut TpzCtx, d_image: *const u8, image_bytes: u64,
+                           d_rec: *const u64, n_records: u32, d_keys: *mut u8, d_kpos: *mut u64,
+                           d_vals: *mut u8, d_vpos: *mut u64, d_info: *mut u64,
+                           stream: *mut c_void) -> TpzErr;
     pub fn tpz_lsm_get_keys(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
                             d_tables: *const tpz_get_table, n_tables: u32,
                             h_level_first: *const u32, n_levels: u32, d_keys: *const u8,

@@ -34,6 +34,8 @@ BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED, BOUND_AFTER = range(4)   # TPZ_
 SCAN_DONE, SCAN_MORE, SCAN_ERROR = range(3)    # tpz_scan_ranges' d_result (TPZ_SCAN_*)
 CUT_NONE, CUT_FOUND, CUT_BAD_ENTRY = range(3)   # tpz_table_cut's d_cut[0] (TPZ_CUT_*)
 MERGE_MAX_RUNS = 256      # TPZ_MERGE_MAX_RUNS
+MEM_REPLAY, MEM_PUT = 0, 1   # tpz_mem_build's mode (TPZ_MEM_REPLAY, TPZ_MEM_PUT)
+WAL_END_IMAGE, WAL_END_EMPTY_KEY, WAL_TRUNCATED = range(3)   # tpz_wal_index's h_info[1] (TPZ_WAL_*)
 MERGE_TILE = 1024         # entries per tile-merge workgroup of tpz_merge_runs (csrc kMergeTile)
 MERGE_LANE_COPY_MAX = 256  # longer keys / values are copied by the whole wave (csrc kLaneCopyMax)
 BLOOM_SLICE_BITS = 1 << 19  # bits per slice of tpz_bloom_build's partitioned path (csrc kBloomSliceBits)
@@ -272,6 +274,19 @@ def lib() -> C.CDLL:
         L.tpz_lsm_scan_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + \
             list(L.tpz_scan_entries.argtypes[1:])
         L.tpz_lsm_scan_entries.restype = C.c_int
+        if not hasattr(L, "tpz_mem_build"):       # (additive within ABI 8: an older build lacks it)
+            raise TpzError(f"{LIB_PATH} does not export tpz_mem_build: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_mem_build.argtypes = [C.c_void_p, C.POINTER(Entries), C.c_uint32] + [C.c_void_p] * 10
+        L.tpz_mem_build.restype = C.c_int
+        if hasattr(L, "tpz_debug_mem_build"):     # diagnostic (not in tpz_gpu.h): membuild_probe.py
+            L.tpz_debug_mem_build.argtypes = list(L.tpz_mem_build.argtypes) + [C.c_uint32]
+            L.tpz_debug_mem_build.restype = C.c_int
+        L.tpz_wal_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tpz_wal_index.restype = C.c_int
+        L.tpz_wal_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32] + \
+            [C.c_void_p] * 6
+        L.tpz_wal_entries.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -601,6 +616,28 @@ class Context:
         """tpz_mem_prefix: the prefix column of a memtable run (n_entries u64 at d_prefix)."""
         check(lib().tpz_mem_prefix(self.handle, C.byref(ent), C.c_void_p(d_prefix),
                                    C.c_void_p(stream)), "tpz_mem_prefix")
+
+    def mem_build_ptrs(self, ent: Entries, mode: int, d_version: int, d_out_keys: int,
+                       d_out_kpos: int, d_out_vals: int, d_out_vpos: int, d_out_prefix: int,
+                       d_src_entry: int, d_out_version: int, d_info: int, stream: int = 0) -> None:
+        """tpz_mem_build: `ent` in arrival order becomes a memtable run under MemTable::open's
+        (MEM_REPLAY) or do_mem_put's (MEM_PUT, d_version: n u64) rule; d_info: 8 u64."""
+        check(lib().tpz_mem_build(self.handle, C.byref(ent), mode, C.c_void_p(d_version),
+                                  C.c_void_p(d_out_keys), C.c_void_p(d_out_kpos),
+                                  C.c_void_p(d_out_vals), C.c_void_p(d_out_vpos),
+                                  C.c_void_p(d_out_prefix), C.c_void_p(d_src_entry),
+                                  C.c_void_p(d_out_version), C.c_void_p(d_info),
+                                  C.c_void_p(stream)), "tpz_mem_build")
+
+    def wal_entries_ptrs(self, d_image: int, image_bytes: int, d_rec: int, n_records: int,
+                         d_keys: int, d_kpos: int, d_vals: int, d_vpos: int, d_info: int,
+                         stream: int = 0) -> None:
+        """tpz_wal_entries: the records of a WAL image in HBM (d_rec: tpz_wal_index's n_records + 1
+        starts) as packed key and value columns in arrival order; d_info: 4 u64."""
+        check(lib().tpz_wal_entries(self.handle, C.c_void_p(d_image), image_bytes,
+                                    C.c_void_p(d_rec), n_records, C.c_void_p(d_keys),
+                                    C.c_void_p(d_kpos), C.c_void_p(d_vals), C.c_void_p(d_vpos),
+                                    C.c_void_p(d_info), C.c_void_p(stream)), "tpz_wal_entries")
 
     def lsm_get_keys_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
                           h_level_first: int, n_levels: int, d_keys: int, d_key_pos: int,

@@ -140,6 +140,7 @@ struct tpz_workspace {
   void* d_comp = nullptr;       // tpz_compress_blocks: the per-block scratch slots + scan parts
   size_t comp_cap = 0;
   void* d_merge = nullptr;      // tpz_merge_runs: prefixes, id lists, tile partitions, scan arrays
+                                // (tpz_mem_build and tpz_wal_entries use it too, in stream order)
   size_t merge_cap = 0;
   void* d_get = nullptr;        // tpz_get_keys: the value-length scan's partial sums
   size_t get_cap = 0;
@@ -1029,6 +1030,103 @@ tpz_err tpz_merge_runs(tpz_ctx* c, const tpz_entries* en, const uint32_t* h_run_
   a.info = d_info;
   a.work = work;
   TPZ_HIP(tpz::launch_merge(a, s));
+  return TPZ_SUCCESS;
+}
+
+// tpz_mem_build, ending after `stop_after` (0: all of it; the diagnostic export below passes 1 or 2).
+static tpz_err mem_build(tpz_ctx* c, const tpz_entries* en, uint32_t mode, const uint64_t* d_version,
+                         uint8_t* d_out_keys, uint64_t* d_out_kpos, uint8_t* d_out_vals,
+                         uint64_t* d_out_vpos, uint64_t* d_out_prefix, uint32_t* d_src_entry,
+                         uint64_t* d_out_version, uint64_t* d_info, void* stream,
+                         uint32_t stop_after) {
+  if (!c || !en || !d_info || !d_out_kpos || !d_out_vpos) return TPZ_ERR_INVALID_ARG;
+  if ((mode != TPZ_MEM_REPLAY && mode != TPZ_MEM_PUT) || en->n_entries == 0xFFFFFFFFu)
+    return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 15u) return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_out_kpos | (uintptr_t)d_out_vpos | (uintptr_t)d_info | (uintptr_t)d_version |
+        (uintptr_t)d_out_prefix | (uintptr_t)d_out_version | (uintptr_t)en->d_kpos |
+        (uintptr_t)en->d_vpos) & 7u) || ((uintptr_t)d_src_entry & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  const uint32_t n = en->n_entries;
+  if (n && (!en->d_kpos || !en->d_vpos || (!en->d_keys && en->key_bytes) ||
+            (!en->d_vals && en->val_bytes) || (!d_out_keys && en->key_bytes) ||
+            (!d_out_vals && en->val_bytes) || (mode == TPZ_MEM_PUT && !d_version)))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    TPZ_HIP(hipMemsetAsync(d_info, 0, 64, s));
+    TPZ_HIP(hipMemsetAsync(d_info + 3, 0xFF, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_out_kpos, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_out_vpos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_merge, &w.merge_cap, tpz::membuild_work_bytes(n));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_merge;
+  }
+  tpz::MemBuildLaunch a{en->d_keys, en->d_kpos, en->key_bytes, en->d_vals, en->d_vpos,
+                        en->val_bytes, n, mode, d_version, d_out_keys, d_out_kpos, d_out_vals,
+                        d_out_vpos, d_out_prefix, d_src_entry, d_out_version, d_info, work,
+                        stop_after};
+  TPZ_HIP(tpz::launch_membuild(a, s));
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_mem_build(tpz_ctx* c, const tpz_entries* en, uint32_t mode, const uint64_t* d_version,
+                      uint8_t* d_out_keys, uint64_t* d_out_kpos, uint8_t* d_out_vals,
+                      uint64_t* d_out_vpos, uint64_t* d_out_prefix, uint32_t* d_src_entry,
+                      uint64_t* d_out_version, uint64_t* d_info, void* stream) {
+  return mem_build(c, en, mode, d_version, d_out_keys, d_out_kpos, d_out_vals, d_out_vpos,
+                   d_out_prefix, d_src_entry, d_out_version, d_info, stream, 0);
+}
+
+// Diagnostic (not in tpz_gpu.h; tools/membuild_probe.py): tpz_mem_build cut short, 1 = after the
+// sort passes, 2 = after the pick and the scan; the outputs are then incomplete.
+extern "C" tpz_err tpz_debug_mem_build(tpz_ctx* c, const tpz_entries* en, uint32_t mode,
+                                       const uint64_t* d_version, uint8_t* d_out_keys,
+                                       uint64_t* d_out_kpos, uint8_t* d_out_vals,
+                                       uint64_t* d_out_vpos, uint64_t* d_out_prefix,
+                                       uint32_t* d_src_entry, uint64_t* d_out_version,
+                                       uint64_t* d_info, void* stream, uint32_t stop_after) {
+  return mem_build(c, en, mode, d_version, d_out_keys, d_out_kpos, d_out_vals, d_out_vpos,
+                   d_out_prefix, d_src_entry, d_out_version, d_info, stream, stop_after);
+}
+
+tpz_err tpz_wal_entries(tpz_ctx* c, const uint8_t* d_image, uint64_t image_bytes,
+                        const uint64_t* d_rec, uint32_t n_records, uint8_t* d_keys,
+                        uint64_t* d_kpos, uint8_t* d_vals, uint64_t* d_vpos, uint64_t* d_info,
+                        void* stream) {
+  if (!c || !d_rec || !d_kpos || !d_vpos || !d_info || n_records == 0xFFFFFFFFu)
+    return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) return TPZ_ERR_INVALID_ARG;
+  if (((uintptr_t)d_rec | (uintptr_t)d_kpos | (uintptr_t)d_vpos | (uintptr_t)d_info) & 7u)
+    return TPZ_ERR_INVALID_ARG;
+  if (n_records && image_bytes && (!d_image || !d_keys || !d_vals)) return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_records == 0) {
+    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
+    TPZ_HIP(hipMemsetAsync(d_info + 3, 0xFF, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_merge, &w.merge_cap, tpz::wal_entries_work_bytes(n_records));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_merge;
+  }
+  tpz::WalEntriesLaunch a{d_image, image_bytes, d_rec, n_records, d_keys, d_kpos, d_vals, d_vpos,
+                          d_info, work};
+  TPZ_HIP(tpz::launch_wal_entries(a, s));
   return TPZ_SUCCESS;
 }
 

@@ -336,6 +336,46 @@ struct MergeLaunch {
 uint64_t merge_work_bytes(uint32_t n, uint32_t n_runs);
 hipError_t launch_merge(const MergeLaunch& a, hipStream_t stream);
 
+// tpz_mem_build (tpz_membuild.hip): a memtable run from entries in arrival order.
+struct MemBuildLaunch {
+  const uint8_t* keys;
+  const uint64_t* kpos;
+  uint64_t key_bytes;
+  const uint8_t* vals;
+  const uint64_t* vpos;
+  uint64_t val_bytes;
+  uint32_t n;                 // > 0
+  uint32_t mode;              // TPZ_MEM_REPLAY / TPZ_MEM_PUT
+  const uint64_t* version;    // n u64 (PUT)
+  uint8_t* out_keys;
+  uint64_t* out_kpos;
+  uint8_t* out_vals;
+  uint64_t* out_vpos;
+  uint64_t* out_prefix;       // or null
+  uint32_t* src_entry;        // or null
+  uint64_t* out_version;      // or null
+  uint64_t* info;             // 8 u64
+  void* work;                 // membuild_work_bytes(n) of device scratch
+  uint32_t stop_after;        // 0; diagnostic: 1 ends after the sort passes, 2 after pick + scan
+};
+uint64_t membuild_work_bytes(uint32_t n);
+hipError_t launch_membuild(const MemBuildLaunch& a, hipStream_t stream);
+// tpz_wal_entries (tpz_membuild.hip): a WAL image's records as packed columns.
+struct WalEntriesLaunch {
+  const uint8_t* img;
+  uint64_t img_bytes;
+  const uint64_t* rec;        // n + 1
+  uint32_t n;                 // > 0
+  uint8_t* keys;
+  uint64_t* kpos;
+  uint8_t* vals;
+  uint64_t* vpos;
+  uint64_t* info;             // 4 u64
+  void* work;                 // wal_entries_work_bytes(n) of device scratch
+};
+uint64_t wal_entries_work_bytes(uint32_t n);
+hipError_t launch_wal_entries(const WalEntriesLaunch& a, hipStream_t stream);
+
 // tpz_get_keys / tpz_get_values (tpz_get.hip): LevelController::get over resident tables.
 struct GetLaunch {
   const tpz_get_table* tabs;    // device

@@ -19,6 +19,7 @@
 //              copied through. partition: one thread per tile boundary bisects the merge path
 //              diagonal in global memory; tile merge: a workgroup stages its <= kMergeTile ids and
 //              prefixes in LDS, every thread bisects its own diagonal there and merges 4 items.
+//              (Both bodies are tpz_merge_dev.h's, which tpz_membuild.hip instantiates too.)
 //   drop       one thread per merged position: the head of its equal-key group by a galloping
 //              bisection backwards (O(log group) compares, not a walk), keep = same run as the head;
 //              writes {keep, kept key bytes, kept value bytes} for the scans
@@ -41,16 +42,18 @@
 
 #include "tpz_copy.h"
 #include "tpz_internal.h"
+#include "tpz_merge_dev.h"
 
 namespace tpz {
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-
-constexpr u32 kMgThreads = 256;
-constexpr u32 kMgPer = kMergeTile / kMgThreads;   // items per thread
-static_assert(kMgPer * kMgThreads == kMergeTile, "tile = threads x items");
+using mergedev::clamp_id;
+using mergedev::kMgThreads;
+using mergedev::Pair;
+using mergedev::span;
+using mergedev::tiles_of;
+using mergedev::u32;
+using mergedev::u64;
 
 struct MergeParams {
   const uint8_t* keys;
@@ -63,49 +66,47 @@ struct MergeParams {
   u32 n_runs;
   const u64* pref;
   u32 run_first[TPZ_MERGE_MAX_RUNS + 1];
+
+  // Lists of a level: list k = runs [k << lvl, (k + 1) << lvl); pair q merges lists 2q (A) and
+  // 2q + 1 (B) into the entry range both cover.
+  __device__ __forceinline__ Pair pair_of(u32 lvl, u32 q) const {
+    const u32 R = n_runs;
+    const u64 w = 1ull << lvl;
+    const u64 r0 = 2 * q * w, r1 = r0 + w, r2 = r1 + w;
+    Pair x;
+    x.a0 = run_first[r0 < R ? r0 : R];
+    x.a1 = run_first[r1 < R ? r1 : R];
+    x.b1 = run_first[r2 < R ? r2 : R];
+    return x;
+  }
+  // The pair that holds index t when every pair takes its tiles plus `extra` slots; k = the index
+  // within the pair, tile0 = the tiles of the pairs before it. False past the last pair.
+  __device__ __forceinline__ bool find_pair(u32 lvl, u32 npairs, u32 t, u32 extra, u32& q, u32& k,
+                                            u32& tile0) const {
+    u32 base = 0;
+    for (u32 i = 0; i < npairs; i++) {
+      const u32 tp = tiles_of(pair_of(lvl, i));
+      if (t < tp + extra) {
+        q = i;
+        k = t;
+        tile0 = base;
+        return true;
+      }
+      t -= tp + extra;
+      base += tp;
+    }
+    return false;
+  }
+  // By key alone: entries are numbered run after run, so "A first on a tie" is the stable merge.
+  __device__ __forceinline__ bool less(u32 a, u64 pa, u32 b, u64 pb) const {
+    if (pa != pb) return pa < pb;
+    return mergedev::tail_cmp(*this, a, b) < 0;
+  }
 };
 
-__device__ __forceinline__ u64 min64(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 max64(u64 a, u64 b) { return a > b ? a : b; }
-
-// Entry e's bytes in a column of `cap` bytes: [at, at + len), clamped to the column.
-__device__ __forceinline__ void span(const u64* pos, u64 cap, u32 e, u64& at, u64& len) {
-  const u64 a = min64(pos[e], cap);
-  const u64 b = min64(max64(pos[e + 1], a), cap);
-  at = a;
-  len = b - a;
+__device__ __forceinline__ int tail_cmp(const MergeParams& p, u32 a, u32 b) {
+  return mergedev::tail_cmp(p, a, b);
 }
-
-__device__ __forceinline__ u64 load_be64(const uint8_t* p) {
-  u64 x;
-  __builtin_memcpy(&x, p, 8);
-  return __builtin_bswap64(x);
-}
-
-// Order of two keys whose 8-byte prefixes are equal: the bytes from offset 8, then the lengths.
-__device__ inline int tail_cmp(const MergeParams& p, u32 a, u32 b) {
-  u64 sa, la, sb, lb;
-  span(p.kpos, p.key_bytes, a, sa, la);
-  span(p.kpos, p.key_bytes, b, sb, lb);
-  const u64 m = min64(la, lb);
-  u64 i = 8;
-  for (; i + 8 <= m; i += 8) {
-    const u64 x = load_be64(p.keys + sa + i), y = load_be64(p.keys + sb + i);
-    if (x != y) return x < y ? -1 : 1;
-  }
-  for (; i < m; i++) {
-    const u32 x = p.keys[sa + i], y = p.keys[sb + i];
-    if (x != y) return x < y ? -1 : 1;
-  }
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
-
-__device__ __forceinline__ bool key_less(const MergeParams& p, u32 a, u64 pa, u32 b, u64 pb) {
-  if (pa != pb) return pa < pb;
-  return tail_cmp(p, a, b) < 0;
-}
-
-__device__ __forceinline__ u32 clamp_id(u32 id, u32 n) { return id < n ? id : n - 1; }
 
 __global__ __launch_bounds__(256) void merge_prefix_kernel(const uint8_t* keys, const u64* kpos,
                                                             u64 key_bytes, u32 n, u64* pref, u32* ids,
@@ -122,62 +123,10 @@ __global__ __launch_bounds__(256) void merge_prefix_kernel(const uint8_t* keys, 
   if (len == 0) atomicMin(reinterpret_cast<unsigned long long*>(info + 3), (unsigned long long)e);
 }
 
-// Lists of a level: list k = runs [k << lvl, (k + 1) << lvl); pair q merges lists 2q (A) and
-// 2q + 1 (B) into the entry range both cover.
-struct Pair {
-  u32 a0, a1, b1;   // A = entries [a0, a1), B = [a1, b1)
-};
-__device__ __forceinline__ Pair pair_of(const MergeParams& p, u32 lvl, u32 q) {
-  const u32 R = p.n_runs;
-  const u64 w = 1ull << lvl;
-  const u64 r0 = 2 * q * w, r1 = r0 + w, r2 = r1 + w;
-  Pair x;
-  x.a0 = p.run_first[r0 < R ? r0 : R];
-  x.a1 = p.run_first[r1 < R ? r1 : R];
-  x.b1 = p.run_first[r2 < R ? r2 : R];
-  return x;
-}
-__device__ __forceinline__ u32 tiles_of(const Pair& x) { return (x.b1 - x.a0 + kMergeTile - 1) / kMergeTile; }
-
-// The pair that holds index t when every pair takes its tiles plus `extra` slots; k = the index
-// within the pair, tile0 = the tiles of the pairs before it. False past the last pair.
-__device__ __forceinline__ bool find_pair(const MergeParams& p, u32 lvl, u32 npairs, u32 t, u32 extra,
-                                          u32& q, u32& k, u32& tile0) {
-  u32 base = 0;
-  for (u32 i = 0; i < npairs; i++) {
-    const u32 tp = tiles_of(pair_of(p, lvl, i));
-    if (t < tp + extra) {
-      q = i;
-      k = t;
-      tile0 = base;
-      return true;
-    }
-    t -= tp + extra;
-    base += tp;
-  }
-  return false;
-}
-
-// part[tile0 + q + k] = how many of the first min(k * kMergeTile, total) merged entries of pair q
-// come from A (the merge path's diagonal; ties take A first: the merge is stable).
+// The partition and the tile merge of a level (tpz_merge_dev.h).
 __global__ __launch_bounds__(256) void merge_partition_kernel(MergeParams p, u32 lvl, u32 npairs,
                                                                u32 nslots, const u32* in, u32* part) {
-  const u32 t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= nslots) return;
-  u32 q, k, tile0;
-  if (!find_pair(p, lvl, npairs, t, 1, q, k, tile0)) return;
-  const Pair x = pair_of(p, lvl, q);
-  const u32 la = x.a1 - x.a0, lb = x.b1 - x.a1;
-  const u64 d64 = (u64)k * kMergeTile;
-  const u32 d = d64 < (u64)la + lb ? (u32)d64 : la + lb;
-  u32 lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
-  for (int it = 0; it < 33 && lo < hi; it++) {
-    const u32 mid = lo + (hi - lo) / 2;
-    const u32 ia = clamp_id(in[x.a0 + mid], p.n), ib = clamp_id(in[x.a1 + (d - 1 - mid)], p.n);
-    if (!key_less(p, ib, p.pref[ib], ia, p.pref[ia])) lo = mid + 1;   // A[mid] goes first
-    else hi = mid;
-  }
-  part[tile0 + q + k] = lo;
+  mergedev::partition_body(p, lvl, npairs, nslots, in, part);
 }
 
 __global__ __launch_bounds__(kMgThreads) void merge_tile_kernel(MergeParams p, u32 lvl, u32 npairs,
@@ -185,58 +134,7 @@ __global__ __launch_bounds__(kMgThreads) void merge_tile_kernel(MergeParams p, u
                                                                  u32* out) {
   __shared__ u64 s_pref[kMergeTile];
   __shared__ u32 s_id[kMergeTile];
-  u32 q, k, tile0;
-  if (!find_pair(p, lvl, npairs, blockIdx.x, 0, q, k, tile0)) return;
-  const Pair x = pair_of(p, lvl, q);
-  const u32 la = x.a1 - x.a0, lb = x.b1 - x.a1;
-  const u32 d0 = k * kMergeTile;                       // (k < tiles_of(x): no overflow)
-  const u32 d1 = la + lb - d0 < kMergeTile ? la + lb : d0 + kMergeTile;
-  // the tile's share of A and B; sorted runs give s0 <= s1 and exact counts, anything else is
-  // cut to the lists
-  const u32 s0 = part[tile0 + q + k];
-  u32 s1 = part[tile0 + q + k + 1];
-  if (s1 < s0) s1 = s0;
-  u32 na = s1 - s0;
-  if (na > d1 - d0) na = d1 - d0;
-  const u32 bs = d0 - s0;
-  u32 nb = d1 - d0 - na;
-  if (nb > lb - bs) nb = lb - bs;
-  const u32 cnt = na + nb;
-  const u32 tid = threadIdx.x;
-  for (u32 i = tid; i < cnt; i += kMgThreads) {
-    const u32 id = clamp_id(i < na ? in[x.a0 + s0 + i] : in[x.a1 + bs + (i - na)], p.n);
-    s_id[i] = id;
-    s_pref[i] = p.pref[id];
-  }
-  __syncthreads();
-  const u32 dt = tid * kMgPer < cnt ? tid * kMgPer : cnt;
-  u32 lo = dt > nb ? dt - nb : 0, hi = dt < na ? dt : na;
-  for (int it = 0; it < 12 && lo < hi; it++) {
-    const u32 mid = lo + (hi - lo) / 2;
-    const u32 jb = na + (dt - 1 - mid);
-    if (!key_less(p, s_id[jb], s_pref[jb], s_id[mid], s_pref[mid])) lo = mid + 1;
-    else hi = mid;
-  }
-  u32 i = lo, j = dt - lo;   // next item of A / of B
-  u32 r[kMgPer];
-#pragma unroll
-  for (u32 t = 0; t < kMgPer; t++) {
-    r[t] = 0;
-    if (dt + t < cnt && (i < na || j < nb)) {
-      bool take_a = j >= nb;
-      if (!take_a && i < na)
-        take_a = !key_less(p, s_id[na + j], s_pref[na + j], s_id[i], s_pref[i]);
-      r[t] = take_a ? s_id[i] : s_id[na + j];
-      if (take_a) i++;
-      else j++;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (u32 t = 0; t < kMgPer; t++)
-    if (tid * kMgPer + t < cnt) s_id[tid * kMgPer + t] = r[t];
-  __syncthreads();
-  for (u32 o = tid; o < cnt; o += kMgThreads) out[x.a0 + d0 + o] = s_id[o];
+  mergedev::tile_body(p, lvl, npairs, in, part, out, s_pref, s_id);
 }
 
 // The run that holds entry id: the largest r with run_first[r] <= id (empty runs share a start

@@ -317,6 +317,19 @@ class DeviceRun:
             ctx.mem_prefix_ptrs(self.entries(), self.prefix.data_ptr(),
                                 torch.cuda.current_stream(self.dev).cuda_stream)
 
+    @classmethod
+    def build(cls, ctx: Context, entries, versions=None, mode=None, prefix: bool = True):
+        """From entries in ARRIVAL order, sorted and deduplicated on the device with the reference's
+        rules (memtable.build_run: tpz_mem_build)."""
+        from .memtable import build_run
+        return build_run(ctx, entries, versions=versions, mode=mode, prefix=prefix)
+
+    @classmethod
+    def from_wal(cls, ctx: Context, image: bytes, prefix: bool = True):
+        """MemTable::open over a WAL image (memtable.replay_wal)."""
+        from .memtable import replay_wal
+        return replay_wal(ctx, image, prefix=prefix)
+
     def entries(self) -> Entries:
         return Entries(self.keys.data_ptr(), self.kpos.data_ptr(), self.vals.data_ptr(),
                        self.vpos.data_ptr(), self.n, self.key_bytes, self.val_bytes)
