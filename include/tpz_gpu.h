@@ -973,6 +973,91 @@ tpz_err tpz_lsm_scan_entries(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n
                              uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
                              void* stream);
 
+/* ---- scanning levels of any width: one merge cursor per level below L0 ----------------------
+ * tpz_lsm_scan_ranges gives every table a lane of the one wave that merges a scan, hence its 64.
+ * Under the reference's defaults (src/opt.rs:31-54, TABLE_CAPACITY in src/table/builder.rs:27) L1
+ * alone holds about 40 tables and L2 about 400. tpz_level_scan_ranges / tpz_level_scan_entries
+ * take tpz_lsm_scan_ranges' / tpz_lsm_scan_entries' arguments (n_runs may be 0) and give their
+ * outputs, with any number of tables inside a level below L0. Additive within ABI 8: new symbols
+ * and constants only (TPZ_HAS_LEVEL_SCAN tells a consumer the header has them).
+ *
+ * Precondition (tpz_get_keys' words): the levels below L0 are stored sorted by smallest key and
+ * are disjoint, and keys increase inside a table. The reference still builds one SsTableIterator
+ * per table that passes the filter (level_tables_sorted, src/level.rs:538-579; lsm_storage.rs:
+ * 350-365), but over such a level those iterators, merged, yield exactly the concatenation of the
+ * surviving tables, so one cursor per level yields the same sequence. A scan's cursors, in
+ * priority order: the runs, newest first; the L0 tables, newest first; one per non-empty level
+ * 1.., in level order. Run and L0 cursors are tpz_lsm_scan_ranges'. A level cursor over the
+ * tables T[0..m) of its level stands for the reference's per-table cursors:
+ *   - Survivors. a = the first table with biggest_key >= lower (0 for Unbounded), z = the last
+ *     with smallest_key <= upper (m - 1 for Unbounded); T[a..z] survive, and with a > z or no
+ *     such table the level contributes nothing. That is level_tables_sorted's filter
+ *     (level.rs:554-568) over a sorted, disjoint level. Both are found by bisection on the
+ *     smallest keys (LevelController::get's partition_point, level.rs:449-451) and one look at a
+ *     biggest key.
+ *   - Creation. T[a] takes the real seek: create_and_seek_to_key and the Excluded / After step
+ *     (lsm_storage.rs:356-362), or create_and_seek_to_first for Unbounded. Every T[j], a < j <= z,
+ *     has smallest_key > biggest_key(T[a]) >= lower, so its create_and_seek_to_key finds block 0
+ *     and bisects there below every key (table/iterator.rs:44-72): the outcome does not depend on
+ *     the scan. It is the table's head record, computed once per call: valid at a (block, entry),
+ *     invalid (MergeIterator::create drops the cursor, merge_iterator.rs:47-57), or failing with
+ *     the status, block and entry tpz_seek_keys reports for a key below all of the table's keys.
+ *     With an Unbounded lower bound the head is create_and_seek_to_first's (table/iterator.rs:
+ *     39-42: block 0, entry 0 and no bisection), kept beside the other.
+ *   - Errors at creation. The reference creates every cursor before it merges, so a failing head
+ *     anywhere in T[a+1..z] makes the scan TPZ_SCAN_ERROR with nothing yielded, however small
+ *     `limit` is; a failing head outside it does nothing. Among several failures the first in the
+ *     reference's per-table cursor order is reported: runs, L0 newest first, the levels, within a
+ *     level the stored order, T[a]'s own seek before any head. A table the reference could not
+ *     have opened keeps tpz_scan_ranges' rule: every scan is an ERROR at the first such table in
+ *     priority order, found before any seek, wherever the scan's range lies.
+ *   - Stepping. When the cursor's table ends (SsTableIterator::next, table/iterator.rs:88-95,
+ *     leaves the last block invalid), the cursor moves to the next table of (current, z] whose
+ *     head is valid and stands at that head; tables with an invalid head are passed over. It never
+ *     enters T[z + 1]: the reference dropped that table, and entering it could yield an element
+ *     through the unchecked-e0 rule (L1 = {a, d}, {f, g}: scan(Excluded(d), Included(e)) yields
+ *     nothing). A T[a] whose own seek is invalid (Excluded at its biggest key) starts at the next
+ *     valid head of (a, z]. The merge is otherwise tpz_lsm_scan_ranges': the tie rule,
+ *     TwoMergeIterator's eager skip (which can carry a level cursor into its next table), the e0
+ *     quirk, TPZ_BOUND_AFTER paging and MergeIterator::next's failure order.
+ *   - Reporting. d_hit_table and d_where name indices into d_tables, never lanes. Over sorted,
+ *     disjoint levels every output equals tpz_lsm_scan_ranges' byte for byte wherever that call
+ *     accepts the set.
+ * With the precondition broken the results are unspecified, but every loop is bounded, every
+ * index clamped, and nothing is written outside the stated capacities. (tpz_scan_ranges and
+ * tpz_lsm_scan_ranges keep merging overlapping lower levels table by table.)
+ *
+ * TPZ_ERR_INVALID_ARG, before any device work: n_runs + L0 tables + non-empty levels below L0 >
+ * TPZ_LEVEL_SCAN_MAX_CURSORS, counted from h_level_first; and everything tpz_lsm_scan_ranges /
+ * tpz_lsm_scan_entries reject apart from their table count. Both calls are asynchronous on
+ * `stream` and use the stream's grow-only workspace; h_level_first is read during the call.
+ * tpz_level_scan_ranges' workspace: per table a 40-byte index record and four u32 links (built on
+ * the device at the start of every call: one thread per table, then one wave per level), then 16
+ * bytes and a status byte per scan and cursor, and the scans' partial sums. A scan reads
+ * O(log tables) smallest keys, one biggest key and two links per level when it is created.
+ * tpz_level_scan_entries is tpz_lsm_scan_entries without the table cap (the gather checks table,
+ * block and entry against the descriptors). */
+#define TPZ_HAS_LEVEL_SCAN 1
+#define TPZ_LEVEL_SCAN_MAX_CURSORS 64u
+
+tpz_err tpz_level_scan_ranges(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                              const tpz_get_table* d_tables, uint32_t n_tables,
+                              const uint32_t* h_level_first, uint32_t n_levels,
+                              const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                              const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                              const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans,
+                              uint32_t limit, uint8_t* d_result, uint8_t* d_status,
+                              uint32_t* d_where, uint32_t* d_hit_table, uint32_t* d_hit_block,
+                              uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
+                              uint64_t* d_val_first, uint64_t* d_info, void* stream);
+tpz_err tpz_level_scan_entries(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                               const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_scans,
+                               uint32_t limit, const uint32_t* d_hit_table,
+                               const uint32_t* d_hit_block, const uint32_t* d_hit_entry,
+                               const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
+                               uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap,
+                               uint64_t* d_vpos, void* stream);
+
 /* ---- building a memtable run: write batches and WAL images ----------------------------------
  * The stage in front of the runs above: entries in ARRIVAL order (a write batch, or the records
  * of a WAL image) become a run (keys strictly increasing, one entry per distinct key) with the

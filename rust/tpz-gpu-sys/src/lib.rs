@@ -79,6 +79,11 @@ pub const TPZ_HAS_MEM: u32 = 1;
 pub const TPZ_MEM_MAX_RUNS: u32 = 16;
 /// `d_table = TPZ_HIT_MEM | run` for a hit in a memtable run.
 pub const TPZ_HIT_MEM: u32 = 0x80000000;
+/// The header declares `tpz_level_scan_ranges` / `tpz_level_scan_entries` (additive within ABI 8):
+/// the scan with one merge cursor per level below L0, so a level may hold any number of tables.
+pub const TPZ_HAS_LEVEL_SCAN: u32 = 1;
+/// The most cursors of one scan: runs + L0 tables + non-empty levels below L0.
+pub const TPZ_LEVEL_SCAN_MAX_CURSORS: u32 = 64;
 
 /// The header declares `tpz_mem_build`, `tpz_wal_index` and `tpz_wal_entries` (additive within
 /// ABI 8): a memtable run built on the device from a write batch or a WAL image.
@@ -364,6 +369,23 @@ extern "C" {
                                 d_hit_entry: *const u32, d_first: *const u64, d_keys: *mut u8,
                                 key_cap: u64, d_kpos: *mut u64, d_vals: *mut u8, val_cap: u64,
                                 d_vpos: *mut u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_level_scan_ranges(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                                 d_tables: *const tpz_get_table, n_tables: u32,
+                                 h_level_first: *const u32, n_levels: u32, d_lo_keys: *const u8,
+                                 d_lo_pos: *const u64, d_lo_kind: *const u8,
+                                 d_hi_keys: *const u8, d_hi_pos: *const u64,
+                                 d_hi_kind: *const u8, n_scans: u32, limit: u32,
+                                 d_result: *mut u8, d_status: *mut u8, d_where: *mut u32,
+                                 d_hit_table: *mut u32, d_hit_block: *mut u32,
+                                 d_hit_entry: *mut u32, d_first: *mut u64,
+                                 d_key_first: *mut u64, d_val_first: *mut u64, d_info: *mut u64,
+                                 stream: *mut c_void) -> TpzErr;
+    pub fn tpz_level_scan_entries(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                                  d_tables: *const tpz_get_table, n_tables: u32, n_scans: u32,
+                                  limit: u32, d_hit_table: *const u32, d_hit_block: *const u32,
+                                  d_hit_entry: *const u32, d_first: *const u64, d_keys: *mut u8,
+                                  key_cap: u64, d_kpos: *mut u64, d_vals: *mut u8, val_cap: u64,
+                                  d_vpos: *mut u64, stream: *mut c_void) -> TpzErr;
     pub fn tpz_scan_ranges(ctx: *mut TpzCtx, d_tables: *const tpz_get_table, n_tables: u32,
                            h_level_first: *const u32, n_levels: u32, d_lo_keys: *const u8,
                            d_lo_pos: *const u64, d_lo_kind: *const u8, d_hi_keys: *const u8,

@@ -28,6 +28,7 @@ GET_MAX_LEVELS = 16       # TPZ_GET_MAX_LEVELS
 GET_ABSENT, GET_FOUND, GET_DELETED, GET_ERROR = range(4)   # tpz_get_keys' d_result (TPZ_GET_*)
 GET_NONE = 0xFFFFFFFF     # d_table / d_block / d_entry of a walk that ended nowhere
 SCAN_MAX_TABLES = 64      # TPZ_SCAN_MAX_TABLES
+LEVEL_SCAN_MAX_CURSORS = 64   # TPZ_LEVEL_SCAN_MAX_CURSORS
 MEM_MAX_RUNS = 16         # TPZ_MEM_MAX_RUNS
 HIT_MEM = 0x80000000      # TPZ_HIT_MEM: d_table = HIT_MEM | run for a hit in a memtable run
 BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED, BOUND_AFTER = range(4)   # TPZ_BOUND_*
@@ -274,6 +275,16 @@ def lib() -> C.CDLL:
         L.tpz_lsm_scan_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + \
             list(L.tpz_scan_entries.argtypes[1:])
         L.tpz_lsm_scan_entries.restype = C.c_int
+        if not hasattr(L, "tpz_level_scan_ranges"):   # (additive within ABI 8)
+            raise TpzError(f"{LIB_PATH} does not export tpz_level_scan_ranges: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_level_scan_ranges.argtypes = list(L.tpz_lsm_scan_ranges.argtypes)
+        L.tpz_level_scan_ranges.restype = C.c_int
+        if hasattr(L, "tpz_debug_level_scan"):    # diagnostic (not in tpz_gpu.h): levelscan_probe.py
+            L.tpz_debug_level_scan.argtypes = list(L.tpz_lsm_scan_ranges.argtypes) + [C.c_uint32]
+            L.tpz_debug_level_scan.restype = C.c_int
+        L.tpz_level_scan_entries.argtypes = list(L.tpz_lsm_scan_entries.argtypes)
+        L.tpz_level_scan_entries.restype = C.c_int
         if not hasattr(L, "tpz_mem_build"):       # (additive within ABI 8: an older build lacks it)
             raise TpzError(f"{LIB_PATH} does not export tpz_mem_build: rebuild (make -C "
                            "topazdb_amd/csrc)")
@@ -696,6 +707,40 @@ class Context:
                                          C.c_void_p(d_keys), key_cap, C.c_void_p(d_kpos),
                                          C.c_void_p(d_vals), val_cap, C.c_void_p(d_vpos),
                                          C.c_void_p(stream)), "tpz_lsm_scan_entries")
+
+    def level_scan_ranges_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                               h_level_first: int, n_levels: int, d_lo_keys: int, d_lo_pos: int,
+                               d_lo_kind: int, d_hi_keys: int, d_hi_pos: int, d_hi_kind: int,
+                               n_scans: int, limit: int, d_result: int, d_status: int,
+                               d_where: int, d_hit_table: int, d_hit_block: int, d_hit_entry: int,
+                               d_first: int, d_key_first: int, d_val_first: int, d_info: int,
+                               stream: int = 0) -> None:
+        """tpz_level_scan_ranges: tpz_lsm_scan_ranges with one merge cursor per run, per L0 table
+        and per non-empty level below L0 (sorted and disjoint), so any number of tables."""
+        ptrs = [C.c_void_p(x) for x in (d_result, d_status, d_where, d_hit_table, d_hit_block,
+                                        d_hit_entry, d_first, d_key_first, d_val_first, d_info)]
+        check(lib().tpz_level_scan_ranges(self.handle, C.c_void_p(d_runs), n_runs,
+                                          C.c_void_p(d_tables), n_tables,
+                                          C.c_void_p(h_level_first), n_levels,
+                                          C.c_void_p(d_lo_keys), C.c_void_p(d_lo_pos),
+                                          C.c_void_p(d_lo_kind), C.c_void_p(d_hi_keys),
+                                          C.c_void_p(d_hi_pos), C.c_void_p(d_hi_kind), n_scans,
+                                          limit, *ptrs, C.c_void_p(stream)),
+              "tpz_level_scan_ranges")
+
+    def level_scan_entries_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                                n_scans: int, limit: int, d_hit_table: int, d_hit_block: int,
+                                d_hit_entry: int, d_first: int, d_keys: int, key_cap: int,
+                                d_kpos: int, d_vals: int, val_cap: int, d_vpos: int,
+                                stream: int = 0) -> None:
+        """tpz_level_scan_entries: the entries tpz_level_scan_ranges yielded."""
+        check(lib().tpz_level_scan_entries(self.handle, C.c_void_p(d_runs), n_runs,
+                                           C.c_void_p(d_tables), n_tables, n_scans, limit,
+                                           C.c_void_p(d_hit_table), C.c_void_p(d_hit_block),
+                                           C.c_void_p(d_hit_entry), C.c_void_p(d_first),
+                                           C.c_void_p(d_keys), key_cap, C.c_void_p(d_kpos),
+                                           C.c_void_p(d_vals), val_cap, C.c_void_p(d_vpos),
+                                           C.c_void_p(stream)), "tpz_level_scan_entries")
 
     def scan_ranges_ptrs(self, d_tables: int, n_tables: int, h_level_first: int, n_levels: int,
                          d_lo_keys: int, d_lo_pos: int, d_lo_kind: int, d_hi_keys: int,

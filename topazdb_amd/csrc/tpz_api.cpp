@@ -1449,6 +1449,137 @@ tpz_err tpz_lsm_scan_entries(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_r
   return TPZ_SUCCESS;
 }
 
+// tpz_level_scan_ranges / tpz_level_scan_entries: any number of tables; the merge wave's lanes go
+// to the cursors (runs, L0 tables, non-empty levels below L0).
+static bool level_scan_shape_ok(uint32_t n_scans, uint32_t limit) {
+  return limit != 0 && (uint64_t)n_scans * limit < (1ull << 32);
+}
+
+static tpz_err level_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                                 const tpz_get_table* d_tables, uint32_t n_tables,
+                                 const uint32_t* h_level_first, uint32_t n_levels,
+                                 const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                                 const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                                 const uint64_t* d_hi_pos, const uint8_t* d_hi_kind,
+                                 uint32_t n_scans, uint32_t limit, uint8_t* d_result,
+                                 uint8_t* d_status, uint32_t* d_where, uint32_t* d_hit_table,
+                                 uint32_t* d_hit_block, uint32_t* d_hit_entry, uint64_t* d_first,
+                                 uint64_t* d_key_first, uint64_t* d_val_first, uint64_t* d_info,
+                                 void* stream, uint32_t stop_after) {
+  if (!c || !d_lo_pos || !d_lo_kind || !d_hi_pos || !d_hi_kind || !d_result || !d_status ||
+      !d_where || !d_hit_table || !d_hit_block || !d_hit_entry || !d_first || !d_key_first ||
+      !d_val_first || !d_info || (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
+    return TPZ_ERR_INVALID_ARG;
+  if (!level_scan_shape_ok(n_scans, limit) || !level_first_ok(h_level_first, n_levels, n_tables))
+    return TPZ_ERR_INVALID_ARG;
+  const uint64_t cursors = tpz::level_scan_cursors(h_level_first, n_levels, n_runs);
+  if (cursors > TPZ_LEVEL_SCAN_MAX_CURSORS) return TPZ_ERR_INVALID_ARG;
+  const uint32_t n_cur = (uint32_t)cursors;
+  if ((((uintptr_t)d_tables | (uintptr_t)d_lo_pos | (uintptr_t)d_hi_pos | (uintptr_t)d_first |
+        (uintptr_t)d_key_first | (uintptr_t)d_val_first | (uintptr_t)d_info) & 7u) ||
+      (((uintptr_t)d_where | (uintptr_t)d_hit_table | (uintptr_t)d_hit_block |
+        (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_key_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_val_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap,
+                     tpz::level_scan_work_bytes(n_scans, n_cur, n_tables));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_scan;
+  }
+  tpz::LevelScanLaunch a{{{d_tables, n_tables, n_levels ? h_level_first[1] : 0u, d_lo_keys,
+                           d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit,
+                           d_result, d_status, d_where, d_hit_table, d_hit_block, d_hit_entry,
+                           d_first, d_key_first, d_val_first, d_info, work}, d_runs, n_runs},
+                         h_level_first, n_levels, stop_after};
+  tpz::launch_level_scan_ranges(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_level_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                              const tpz_get_table* d_tables, uint32_t n_tables,
+                              const uint32_t* h_level_first, uint32_t n_levels,
+                              const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                              const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                              const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans,
+                              uint32_t limit, uint8_t* d_result, uint8_t* d_status,
+                              uint32_t* d_where, uint32_t* d_hit_table, uint32_t* d_hit_block,
+                              uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
+                              uint64_t* d_val_first, uint64_t* d_info, void* stream) {
+  return level_scan_ranges(c, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels,
+                           d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans,
+                           limit, d_result, d_status, d_where, d_hit_table, d_hit_block,
+                           d_hit_entry, d_first, d_key_first, d_val_first, d_info, stream, 0);
+}
+
+// Diagnostic (not in tpz_gpu.h; tools/levelscan_probe.py): tpz_level_scan_ranges cut short, 1 =
+// after the per-call index, 2 = after the links; the outputs are then not written.
+extern "C" tpz_err tpz_debug_level_scan(
+    tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs, const tpz_get_table* d_tables,
+    uint32_t n_tables, const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_lo_keys,
+    const uint64_t* d_lo_pos, const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+    const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans, uint32_t limit,
+    uint8_t* d_result, uint8_t* d_status, uint32_t* d_where, uint32_t* d_hit_table,
+    uint32_t* d_hit_block, uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
+    uint64_t* d_val_first, uint64_t* d_info, void* stream, uint32_t stop_after) {
+  return level_scan_ranges(c, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels,
+                           d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans,
+                           limit, d_result, d_status, d_where, d_hit_table, d_hit_block,
+                           d_hit_entry, d_first, d_key_first, d_val_first, d_info, stream,
+                           stop_after);
+}
+
+tpz_err tpz_level_scan_entries(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                               const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_scans,
+                               uint32_t limit, const uint32_t* d_hit_table,
+                               const uint32_t* d_hit_block, const uint32_t* d_hit_entry,
+                               const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
+                               uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap,
+                               uint64_t* d_vpos, void* stream) {
+  if (!c || !d_kpos || !d_vpos || (n_tables && !d_tables) || (key_cap && !d_keys) ||
+      (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
+      (n_scans && (!d_hit_table || !d_hit_block || !d_hit_entry || !d_first)))
+    return TPZ_ERR_INVALID_ARG;
+  if (!level_scan_shape_ok(n_scans, limit)) return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
+      (((uintptr_t)d_tables | (uintptr_t)d_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u) ||
+      (((uintptr_t)d_hit_table | (uintptr_t)d_hit_block | (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_entries_work_bytes(n_scans));
+    if (r != TPZ_SUCCESS) return r;
+    work = w.d_scan;
+  }
+  tpz::LsmScanEntriesLaunch a{{d_tables, n_tables, n_scans, limit, d_hit_table, d_hit_block,
+                               d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals, val_cap,
+                               d_vpos, work}, d_runs, n_runs};
+  tpz::launch_lsm_scan_entries(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
 tpz_err tpz_flat_entry_pos(tpz_ctx* c, const tpz_flat_columns* cols, uint32_t n_blocks,
                            uint64_t* d_kpos, uint64_t* d_vpos, uint32_t* d_info, void* stream) {
   if (!c || !cols || !d_kpos || !d_vpos || !d_info) return TPZ_ERR_INVALID_ARG;

@@ -488,6 +488,18 @@ struct LsmScanEntriesLaunch {
   uint32_t n_runs;
 };
 void launch_lsm_scan_entries(const LsmScanEntriesLaunch& a, hipStream_t stream);
+// tpz_level_scan_ranges (tpz_levelscan.hip): the same scan with one cursor per run, per L0 table
+// and per non-empty level below L0. work: level_scan_work_bytes(n_scans, level_scan_cursors(..),
+// n_tables) of device scratch. (tpz_level_scan_entries is launch_lsm_scan_entries.)
+struct LevelScanLaunch {
+  LsmScanLaunch lsm;            // n_tables: any number
+  const uint32_t* level_first;  // host: n_levels + 1, checked by the caller
+  uint32_t n_levels;
+  uint32_t stop_after;          // 0; diagnostic: 1 ends after the index pass, 2 after the links
+};
+uint64_t level_scan_cursors(const uint32_t* level_first, uint32_t n_levels, uint32_t n_runs);
+uint64_t level_scan_work_bytes(uint32_t n_scans, uint32_t n_cursors, uint32_t n_tables);
+void launch_level_scan_ranges(const LevelScanLaunch& a, hipStream_t stream);
 
 // tpz_entries_bound / tpz_table_cut / tpz_sst_finish (tpz_tables.hip): a compaction task's key
 // ranges, table cuts and SST file images.

@@ -3,6 +3,8 @@
 // tpz_lsm_scan_entries: the whole scan, memtable runs merged in). kMem = false is the SST half as
 // it always was; kMem = true puts one cursor per run in front of the tables' (a wave's lanes
 // 0 .. n_runs - 1, the newest run first) and adds TwoMergeIterator's eager step to the merge.
+// kLvl (tpz_levelscan.hip: tpz_level_scan_ranges) gives a lane to every non-empty level below L0
+// instead of to every table of it: a level lane's cursor walks the level's surviving tables.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -92,15 +94,66 @@ __device__ __forceinline__ u32 run_land(const tpz_entries& e, Cur& c) {
   memdev::run_value(e, c.e, c.vlen);
   return kValid;
 }
+// The level scan's per-call index of a table (tpz_levelscan_dev.h index_body): whether the
+// reference could have opened it (os: 0, or the status | kUnopened; ob: the block), its biggest
+// key, and its head: where a cursor created below all of its keys stands ([0]: by
+// create_and_seek_to_key, [1]: by create_and_seek_to_first), or how creating it fails.
+struct TabIndex {
+  const uint8_t* big;
+  u32 bigl;
+  u32 ob;
+  u32 hb[2], he[2];      // block and entry
+  uint8_t hk[2];         // kValid / kInvalid / kFail
+  uint8_t hs[2];         // the status of a failing head
+  uint8_t os;
+};
+// What the level scan's seek and merge read beside the tables (kLvl).
+struct Levels {
+  const tpz_get_table* tabs;
+  u32 n_tables;
+  const TabIndex* idx;
+  const u32* nf;             // 2 x n_tables: the next table at or after t whose head fails
+  const u32* nv;             // 2 x n_tables: ... whose head is valid (kNone: none in the level)
+  const u32* first_unopened; // one u32: the first table that cannot be opened, in priority order
+  u32 n_cur;                 // cursors per scan: runs + L0 tables + non-empty levels below L0
+};
+
+// A table cursor's next. kLvl: a level's cursor at the end of table t enters the next table of
+// (t, z] whose head is valid, at that head (the reference created that table's cursor there when
+// the scan began; the tables between have invalid heads, and MergeIterator::create dropped them).
+// Only the end of a table pays for it: the step within a table is advance alone.
+template <bool kLvl>
+__device__ __forceinline__ u32 table_step(const tpz_table*& tab, u32& t, u32 z, u32 kd, Cur& c,
+                                          u32& fst, const Levels& L) {
+  u32 r = advance(*tab, c, fst);
+  if (kLvl && r == kInvalid && t < z) {
+    const u32 v = L.nv[(u64)kd * L.n_tables + t + 1];
+    if (v <= z && v < L.n_tables) {
+      const TabIndex& x = L.idx[v];
+      t = v;
+      tab = &L.tabs[v].table;
+      c.b = x.hb[kd];
+      c.e = x.he[kd];
+      if (c.b < tab->n_blocks) {
+        const u32 bst = tab->d_status[c.b];
+        if (block_decoded(bst)) {
+          open_block(*tab, c, c.b, bst);
+          r = land(c, fst);
+        }
+      }
+    }
+  }
+  return r;
+}
 // A cursor's next: the table's, or the run's (which cannot fail).
-template <bool kMem>
-__device__ __forceinline__ u32 step(const tpz_table* tab, const tpz_mem_run* run, Cur& c,
-                                    u32& fst) {
+template <bool kMem, bool kLvl>
+__device__ __forceinline__ u32 step(const tpz_table*& tab, const tpz_mem_run* run, u32& t, u32 z,
+                                    u32 kd, Cur& c, u32& fst, const Levels& L) {
   if (kMem && run) {
     c.e++;
     return run_land(run->entries, c);
   }
-  return advance(*tab, c, fst);
+  return table_step<kLvl>(tab, t, z, kd, c, fst, L);
 }
 
 // SsTable::open's init_samllest_biggest_key (table.rs:143-151): the last entry's key of the last
@@ -123,6 +176,47 @@ __device__ __forceinline__ bool biggest_key(const tpz_table& t, const uint8_t*& 
   if (v.seek_panics(0) || v.seek_panics(n - 1)) return false;   // seek_to_first, seek_to_last
   k = seekdev::entry_key(v, n - 1, kl);
   return kl > 0;                                 // assert!(iter.is_valid())
+}
+
+// map.range((lower, upper)) (src/mem_table.rs:199-219) as entries [lb, ub): the cursor is
+// (lb, ub), or (kNone, kNone) where it starts invalid (an empty range, or the empty key first:
+// MergeIterator::create drops it).
+__device__ __forceinline__ void run_range(const tpz_mem_run& run, u32 lk, u32 hk, const uint8_t* lo,
+                                          u64 lol, const uint8_t* hi, u64 hil, u32& b, u32& e) {
+  const u32 n = run.entries.n_entries;
+  const u32 lb = lk == TPZ_BOUND_UNBOUNDED
+                     ? 0u : memdev::run_bound(run, lo, lol, key_prefix(lo, lol),
+                                              lk != TPZ_BOUND_INCLUDED);
+  const u32 ub = hk == TPZ_BOUND_UNBOUNDED
+                     ? n : memdev::run_bound(run, hi, hil, key_prefix(hi, hil),
+                                             hk == TPZ_BOUND_INCLUDED);
+  if (lb < ub && lb < n) {
+    u64 kl;
+    memdev::run_key(run.entries, lb, kl);
+    if (kl) {
+      b = lb;
+      e = ub < n ? ub : n;
+    }
+  }
+}
+
+// The cursor of a surviving table (lsm_storage.rs:350-365): create_and_seek_to_first for an
+// Unbounded lower bound, else create_and_seek_to_key and the Excluded / After step. (c.b, c.e) is
+// where it stands, or with kFail where the reference fails and `fst` how.
+__device__ __forceinline__ u32 seek_lower(const tpz_table& tab, u32 lk, const uint8_t* lo, u64 lol,
+                                          Cur& c, u32& fst) {
+  if (lk == TPZ_BOUND_UNBOUNDED) return first_of_block(tab, c, 0, fst);   // create_and_seek_to_first
+  const seekdev::SeekPos s = seekdev::seek_table(tab, lo, lol);           // create_and_seek_to_key
+  c.b = s.block;
+  c.e = s.entry;
+  fst = s.status;
+  u32 r = s.status != TPZ_BLOCK_OK ? kFail : s.valid ? kValid : kInvalid;
+  if (r == kValid && lk != TPZ_BOUND_INCLUDED) {   // lsm_storage.rs:356-362
+    open_block(tab, c, c.b, tab.d_status[c.b]);
+    c.key = seekdev::entry_key(c.v, c.e, c.klen);
+    if (c.klen == lol && seekdev::key_cmp(c.key, c.klen, lo, lol) == 0) r = advance(tab, c, fst);
+  }
+  return r;
 }
 
 struct SeekParams {
@@ -157,25 +251,7 @@ __device__ __forceinline__ void seek_body(const SeekParams& p, const Runs& m) {
     const uint8_t* hi = p.hi + ha;
     const u64 lol = p.lo_pos[i + 1] - la, hil = p.hi_pos[i + 1] - ha;
     if (kMem && pc < m.n_runs) {
-      // map.range((lower, upper)) (src/mem_table.rs:199-219) as entries [lb, ub): the cursor is
-      // (lb, ub), or (kNone, kNone) where it starts invalid (an empty range, or the empty key
-      // first: MergeIterator::create drops it)
-      const tpz_mem_run& run = m.runs[m.n_runs - 1 - pc];       // view().iter().rev()
-      const u32 n = run.entries.n_entries;
-      const u32 lb = lk == TPZ_BOUND_UNBOUNDED
-                         ? 0u : memdev::run_bound(run, lo, lol, key_prefix(lo, lol),
-                                                  lk != TPZ_BOUND_INCLUDED);
-      const u32 ub = hk == TPZ_BOUND_UNBOUNDED
-                         ? n : memdev::run_bound(run, hi, hil, key_prefix(hi, hil),
-                                                 hk == TPZ_BOUND_INCLUDED);
-      if (lb < ub && lb < n) {
-        u64 kl;
-        memdev::run_key(run.entries, lb, kl);
-        if (kl) {
-          b = lb;
-          e = ub < n ? ub : n;
-        }
-      }
+      run_range(m.runs[m.n_runs - 1 - pc], lk, hk, lo, lol, hi, hil, b, e);   // view().rev()
     } else {
       const u32 t = table_of(kMem ? pc - m.n_runs : pc, p.l0);
       const tpz_table& tab = p.tabs[t].table;
@@ -194,22 +270,7 @@ __device__ __forceinline__ void seek_body(const SeekParams& p, const Runs& m) {
         }
         if (keep) {
           Cur c;
-          u32 r;
-          if (lk == TPZ_BOUND_UNBOUNDED) {           // create_and_seek_to_first
-            r = first_of_block(tab, c, 0, fst);
-          } else {                                   // create_and_seek_to_key
-            const seekdev::SeekPos s = seekdev::seek_table(tab, lo, lol);
-            c.b = s.block;
-            c.e = s.entry;
-            fst = s.status;
-            r = s.status != TPZ_BLOCK_OK ? kFail : s.valid ? kValid : kInvalid;
-            if (r == kValid && lk != TPZ_BOUND_INCLUDED) {   // lsm_storage.rs:356-362
-              open_block(tab, c, c.b, tab.d_status[c.b]);
-              c.key = seekdev::entry_key(c.v, c.e, c.klen);
-              if (c.klen == lol && seekdev::key_cmp(c.key, c.klen, lo, lol) == 0)
-                r = advance(tab, c, fst);
-            }
-          }
+          const u32 r = seek_lower(tab, lk, lo, lol, c, fst);
           if (r != kInvalid) {
             b = c.b;
             e = c.e;
@@ -251,37 +312,56 @@ struct MergeParams {
   u64* val_first;
 };
 
-// One wave per scan, one cursor per lane in priority order.
-template <bool kMem>
-__device__ __forceinline__ void merge_body(const MergeParams& p, const Runs& m) {
+// One wave per scan, one cursor per lane in priority order. kLvl: the seek stored (table, block,
+// entry, z) per cursor, and a lane's table changes as a level's cursor walks on.
+template <bool kMem, bool kLvl = false>
+__device__ __forceinline__ void merge_body(const MergeParams& p, const Runs& m,
+                                           const Levels& L = Levels{}) {
   const u32 lane = copydev::lane_id();
   const u32 i = blockIdx.x * kWaves + threadIdx.x / 64;
   if (i >= p.n_scans) return;                    // (the whole wave)
   const u32 n_runs = kMem ? m.n_runs : 0u;
-  const u32 n_cur = p.n_tables + n_runs;
+  const u32 n_cur = kLvl ? L.n_cur : p.n_tables + n_runs;
   const u32 lk = p.lo_kind[i], hk = p.hi_kind[i];
+  const u32 fu = kLvl ? *L.first_unopened : kNone;
   u32 res = TPZ_SCAN_DONE, st = TPZ_BLOCK_OK, w0 = kNone, w1 = kNone, w2 = kNone, count = 0;
   u64 kb = 0, vb = 0;
   if (lk > TPZ_BOUND_AFTER || hk > TPZ_BOUND_EXCLUDED) {
     res = TPZ_SCAN_ERROR;
     st = TPZ_BLOCK_MALFORMED;
+  } else if (kLvl && fu != kNone) {              // found before any seek (tpz_levelscan_dev.h)
+    res = TPZ_SCAN_ERROR;
+    st = L.idx[fu].os & ~kUnopened;
+    w0 = fu;
+    w1 = L.idx[fu].ob;
   } else {
     Cur c;
     c.b = c.e = kNone;
     c.n = 0;
     c.key = nullptr;
     c.klen = c.vlen = 0;
-    u32 cs = TPZ_BLOCK_OK, t = 0;
+    u32 cs = TPZ_BLOCK_OK, t = 0, z = 0;
+    const u32 kd = lk == TPZ_BOUND_UNBOUNDED ? 1u : 0u;   // (kLvl: the head a level's tables take)
     const tpz_table* tab = nullptr;
     const tpz_mem_run* run = nullptr;
     if (lane < n_cur) {
       const u64 g = (u64)i * n_cur + lane;
-      c.b = p.cur[2 * g];
-      c.e = p.cur[2 * g + 1];
+      if (kLvl) {
+        const uint4 q = reinterpret_cast<const uint4*>(p.cur)[g];
+        t = q.x;
+        c.b = q.y;
+        c.e = q.z;
+        z = q.w;
+      } else {
+        c.b = p.cur[2 * g];
+        c.e = p.cur[2 * g + 1];
+      }
       cs = p.cst[g];
       if (kMem && lane < n_runs) {
         t = TPZ_HIT_MEM | (n_runs - 1 - lane);
         run = &m.runs[n_runs - 1 - lane];
+      } else if (kLvl) {
+        if (t < p.n_tables) tab = &p.tabs[t].table;         // (kNone: the cursor has no table)
       } else {
         t = table_of(lane - n_runs, p.l0);
         tab = &p.tabs[t].table;
@@ -356,7 +436,7 @@ __device__ __forceinline__ void merge_body(const MergeParams& p, const Runs& m) 
           const u64 skip = eq & sst_lanes;
           if ((skip >> lane) & 1) {
             do {
-              r = advance(*tab, c, fst);
+              r = table_step<kLvl>(tab, t, z, kd, c, fst, L);
             } while (r == kValid && c.klen == lklen &&
                      seekdev::key_cmp(c.key, c.klen, lkey, lklen) == 0);
             live = r == kValid;
@@ -401,10 +481,10 @@ __device__ __forceinline__ void merge_body(const MergeParams& p, const Runs& m) 
         r = kValid;
         if ((eq >> lane) & 1) {
           if (lane == (u32)ld) {
-            r = step<kMem>(tab, run, c, fst);
+            r = step<kMem, kLvl>(tab, run, t, z, kd, c, fst, L);
           } else {
             do {
-              r = step<kMem>(tab, run, c, fst);
+              r = step<kMem, kLvl>(tab, run, t, z, kd, c, fst, L);
             } while (r == kValid && c.klen == lklen &&
                      seekdev::key_cmp(c.key, c.klen, lkey, lklen) == 0);
           }

@@ -18,13 +18,18 @@ descriptor per table once, and answers
   scan(lower, upper)
                     the reference's FusedIterator<LsmIterator>, pulled page by page
 
+A set of more than 64 tables (runs included) is scanned with tpz_level_scan_ranges /
+tpz_level_scan_entries instead: one merge cursor per run, per L0 table and per non-empty level below
+L0, so a level may hold any number of tables; runs + L0 tables + non-empty lower levels <= 64.
+`by_level=True` on scan_ranges / scan_batch takes that path for a smaller set too.
+
 `DeviceRun(ctx, entries)` is one memtable's sorted snapshot in HBM (a tpz_mem_run, with its prefix
 column), and `DeviceLsm(ctx, runs, levels)` answers LsmStorage::get (src/lsm_storage.rs:198-213)
 and LsmStorage::scan (:335-374, the memtables merged in with TwoMergeIterator) over runs plus
 tables: `get_batch`, `get`, `scan_batch` and `scan` shaped exactly like DeviceLevels'.
 
 There is no CPU fallback: the walk, the merge and the gathers are the kernels of csrc/tpz_get.hip,
-csrc/tpz_scan.hip and csrc/tpz_mem.hip.
+csrc/tpz_scan.hip, csrc/tpz_mem.hip and csrc/tpz_levelscan.hip.
 """
 from __future__ import annotations
 
@@ -119,6 +124,8 @@ class DeviceLevels:
         np.cumsum([len(lv) for lv in self.levels], out=self.level_first[1:])
         self.n_tables = len(self.tables)
         self.n_levels = len(self.levels)
+        # the level scan's cursors: one per L0 table and per non-empty level below L0
+        self.n_cursors = sum(len(lv) if i == 0 else bool(lv) for i, lv in enumerate(self.levels))
         desc = (GetTable * max(self.n_tables, 1))()
         for i, t in enumerate(self.tables):
             dt = _device_table(t)
@@ -177,10 +184,12 @@ class DeviceLevels:
         out["values"] = vals.cpu().numpy().tobytes()
         return out
 
-    def scan_ranges(self, ranges: list, limit: int) -> dict:
+    def scan_ranges(self, ranges: list, limit: int, by_level: bool = False) -> dict:
         """tpz_scan_ranges on the current stream: device tensors result, status (uint8), where
         (int32, n x 3), hit_table, hit_block, hit_entry (int32, n x limit), first, key_first,
-        val_first (int64, n + 1), info (int64, 3), and n, limit."""
+        val_first (int64, n + 1), info (int64, 3), and n, limit. More than SCAN_MAX_TABLES tables,
+        or by_level: tpz_level_scan_ranges (one cursor per level below L0)."""
+        by_level = by_level or self.n_tables > _lib.SCAN_MAX_TABLES
         n = len(ranges)
         lo = [_bound(r[0], True) for r in ranges]
         hi = [_bound(r[1], False) for r in ranges]
@@ -197,14 +206,17 @@ class DeviceLevels:
         for k in ("first", "key_first", "val_first"):
             out[k] = torch.empty(n + 1, dtype=torch.int64, device=dev)
         out["info"] = torch.empty(3, dtype=torch.int64, device=dev)
-        self.ctx.scan_ranges_ptrs(self.d_tables.data_ptr(), self.n_tables,
-                                  self.level_first.ctypes.data, self.n_levels,
-                                  *(c.data_ptr() for c in cols), n, limit,
-                                  *(out[k].data_ptr() for k in
-                                    ("result", "status", "where", "hit_table", "hit_block",
-                                     "hit_entry", "first", "key_first", "val_first", "info")),
-                                  torch.cuda.current_stream(dev).cuda_stream)
-        out["n"], out["limit"] = n, limit
+        args = (self.d_tables.data_ptr(), self.n_tables, self.level_first.ctypes.data,
+                self.n_levels, *(c.data_ptr() for c in cols), n, limit,
+                *(out[k].data_ptr() for k in
+                  ("result", "status", "where", "hit_table", "hit_block", "hit_entry", "first",
+                   "key_first", "val_first", "info")),
+                torch.cuda.current_stream(dev).cuda_stream)
+        if by_level:
+            self.ctx.level_scan_ranges_ptrs(0, 0, *args)
+        else:
+            self.ctx.scan_ranges_ptrs(*args)
+        out["n"], out["limit"], out["by_level"] = n, limit, by_level
         out["_bounds"] = cols        # alive until the stream has run the scan
         return out
 
@@ -217,16 +229,19 @@ class DeviceLevels:
                "vpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
                "keys": torch.empty(max(kbytes, 1), dtype=torch.uint8, device=dev),
                "values": torch.empty(max(vbytes, 1), dtype=torch.uint8, device=dev)}
-        self.ctx.scan_entries_ptrs(self.d_tables.data_ptr(), self.n_tables, s["n"], s["limit"],
-                                   s["hit_table"].data_ptr(), s["hit_block"].data_ptr(),
-                                   s["hit_entry"].data_ptr(), s["first"].data_ptr(),
-                                   out["keys"].data_ptr(), kbytes, out["kpos"].data_ptr(),
-                                   out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
-                                   torch.cuda.current_stream(dev).cuda_stream)
+        args = (self.d_tables.data_ptr(), self.n_tables, s["n"], s["limit"],
+                s["hit_table"].data_ptr(), s["hit_block"].data_ptr(), s["hit_entry"].data_ptr(),
+                s["first"].data_ptr(), out["keys"].data_ptr(), kbytes, out["kpos"].data_ptr(),
+                out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream)
+        if s.get("by_level"):
+            self.ctx.level_scan_entries_ptrs(0, 0, *args)
+        else:
+            self.ctx.scan_entries_ptrs(*args)
         out["keys"], out["values"] = out["keys"][:kbytes], out["values"][:vbytes]
         return out
 
-    def scan_batch(self, ranges: list, limit: int) -> dict:
+    def scan_batch(self, ranges: list, limit: int, by_level: bool = False) -> dict:
         """LsmStorage::scan's SST half for every (lower, upper) of `ranges`, at most `limit`
         entries each; a bound is None (Unbounded), ("in", key), ("ex", key) or, as a lower bound
         only, ("after", key). Numpy arrays: result (SCAN_DONE / SCAN_MORE / SCAN_ERROR), status,
@@ -234,8 +249,8 @@ class DeviceLevels:
         hit_block, hit_entry (n x limit uint32; a row is defined up to the scan's count), first,
         key_first, val_first (n + 1 uint64); kpos, vpos (entries + 1 uint64) and keys, values
         (bytes): scan i owns entries [first[i], first[i + 1]) in iterator order, entry j's key
-        is keys[kpos[j]:kpos[j + 1]]."""
-        s = self.scan_ranges(ranges, limit)
+        is keys[kpos[j]:kpos[j + 1]]. by_level: as for scan_ranges."""
+        s = self.scan_ranges(ranges, limit, by_level)
         n = s["n"]
         totals = s["info"].cpu().numpy()             # the one read-back between the two calls
         e = self.scan_entries(s, totals)
@@ -349,9 +364,9 @@ class DeviceLsm(DeviceLevels):
         if len(runs) > _lib.MEM_MAX_RUNS:
             raise ValueError(f"{len(runs)} runs: at most {_lib.MEM_MAX_RUNS}")
         super().__init__(ctx, levels)
-        if len(runs) + self.n_tables > _lib.SCAN_MAX_TABLES:
-            raise ValueError(f"{len(runs)} runs and {self.n_tables} tables: at most "
-                             f"{_lib.SCAN_MAX_TABLES} cursors")
+        if len(runs) + self.n_cursors > _lib.LEVEL_SCAN_MAX_CURSORS:
+            raise ValueError(f"{len(runs)} runs and {self.n_cursors} table cursors (L0 tables plus "
+                             f"non-empty lower levels): at most {_lib.LEVEL_SCAN_MAX_CURSORS}")
         self.runs = list(runs)
         self.n_runs = len(self.runs)
         desc = (MemRun * max(self.n_runs, 1))()
@@ -392,8 +407,10 @@ class DeviceLsm(DeviceLevels):
                                      torch.cuda.current_stream(self.dev).cuda_stream)
         return vals[:total]
 
-    def scan_ranges(self, ranges: list, limit: int) -> dict:
-        """tpz_lsm_scan_ranges on the current stream: DeviceLevels.scan_ranges' outputs."""
+    def scan_ranges(self, ranges: list, limit: int, by_level: bool = False) -> dict:
+        """tpz_lsm_scan_ranges on the current stream: DeviceLevels.scan_ranges' outputs. More than
+        SCAN_MAX_TABLES runs plus tables, or by_level: tpz_level_scan_ranges."""
+        by_level = by_level or self.n_runs + self.n_tables > _lib.SCAN_MAX_TABLES
         n = len(ranges)
         lo = [_bound(r[0], True) for r in ranges]
         hi = [_bound(r[1], False) for r in ranges]
@@ -410,14 +427,14 @@ class DeviceLsm(DeviceLevels):
         for k in ("first", "key_first", "val_first"):
             out[k] = torch.empty(n + 1, dtype=torch.int64, device=dev)
         out["info"] = torch.empty(3, dtype=torch.int64, device=dev)
-        self.ctx.lsm_scan_ranges_ptrs(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(),
-                                      self.n_tables, self.level_first.ctypes.data, self.n_levels,
-                                      *(c.data_ptr() for c in cols), n, limit,
-                                      *(out[k].data_ptr() for k in
-                                        ("result", "status", "where", "hit_table", "hit_block",
-                                         "hit_entry", "first", "key_first", "val_first", "info")),
-                                      torch.cuda.current_stream(dev).cuda_stream)
-        out["n"], out["limit"] = n, limit
+        call = self.ctx.level_scan_ranges_ptrs if by_level else self.ctx.lsm_scan_ranges_ptrs
+        call(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(), self.n_tables,
+             self.level_first.ctypes.data, self.n_levels, *(c.data_ptr() for c in cols), n, limit,
+             *(out[k].data_ptr() for k in
+               ("result", "status", "where", "hit_table", "hit_block", "hit_entry", "first",
+                "key_first", "val_first", "info")),
+             torch.cuda.current_stream(dev).cuda_stream)
+        out["n"], out["limit"], out["by_level"] = n, limit, by_level
         out["_bounds"] = cols        # alive until the stream has run the scan
         return out
 
@@ -429,13 +446,13 @@ class DeviceLsm(DeviceLevels):
                "vpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
                "keys": torch.empty(max(kbytes, 1), dtype=torch.uint8, device=dev),
                "values": torch.empty(max(vbytes, 1), dtype=torch.uint8, device=dev)}
-        self.ctx.lsm_scan_entries_ptrs(self.d_runs.data_ptr(), self.n_runs,
-                                       self.d_tables.data_ptr(), self.n_tables, s["n"], s["limit"],
-                                       s["hit_table"].data_ptr(), s["hit_block"].data_ptr(),
-                                       s["hit_entry"].data_ptr(), s["first"].data_ptr(),
-                                       out["keys"].data_ptr(), kbytes, out["kpos"].data_ptr(),
-                                       out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream)
+        call = (self.ctx.level_scan_entries_ptrs if s.get("by_level")
+                else self.ctx.lsm_scan_entries_ptrs)
+        call(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(), self.n_tables, s["n"],
+             s["limit"], s["hit_table"].data_ptr(), s["hit_block"].data_ptr(),
+             s["hit_entry"].data_ptr(), s["first"].data_ptr(), out["keys"].data_ptr(), kbytes,
+             out["kpos"].data_ptr(), out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
+             torch.cuda.current_stream(dev).cuda_stream)
         out["keys"], out["values"] = out["keys"][:kbytes], out["values"][:vbytes]
         return out
 
