@@ -1248,6 +1248,88 @@ tpz_err tpz_sst_finish(tpz_ctx* ctx, const tpz_entries* entries, const tpz_sst_i
                        uint32_t n_images, uint32_t max_blocks, uint8_t* d_base,
                        uint64_t span_bytes, uint64_t* d_info, void* stream);
 
+/* ---- opening SST file images that are resident in HBM -------------------------------------
+ * SsTable::open's parse (src/table.rs:91-112: read_bloom :75-87, the meta offset :93-97,
+ * BlockMeta::decode_block_meta :49-59) for a batch of whole file images that already lie in one
+ * device buffer, as tpz_sst_finish leaves them or as tpz_verify_files takes them. Additive within
+ * ABI 8: new symbols and constants only (TPZ_HAS_OPEN tells a consumer the header has them). The
+ * outputs are what a tpz_table / tpz_get_table needs besides the decoded columns: every block's
+ * extent (the decode's d_ext), the block first keys with their positions, and where the bloom
+ * filter lies in the image; nothing is copied to the host and the image is never written.
+ *
+ * File f is d_src[d_span[2f] .. d_span[2f] + d_span[2f + 1]): the whole file, its 4-byte CRC
+ * trailer included (FileObject::size() = len - 4, src/table/file_object.rs:29-31, :63). The spans
+ * lie inside [0, span_bytes), in increasing address order, and do not overlap; any bytes may lie
+ * between them. The calls read nothing outside the spans. A file that starts before its
+ * predecessor ends, or ends past span_bytes, is TPZ_OPEN_UNSUPPORTED; whatever the spans hold,
+ * every access stays inside the spans, the scratch and the stated capacities.
+ *
+ * tpz_open_index, per file:
+ *   d_info  8 u64: {status, size, meta offset, meta bytes, bloom offset or UINT64_MAX,
+ *           filter_len, n_blocks, flags}; size = len - 4 (0 when len < 4); with a status other
+ *           than TPZ_OPEN_OK every field after size is 0. flags bit 0 is set by tpz_open_metas.
+ *   status, check by check in the reference's order:
+ *     TPZ_OPEN_SHORT           len < 8: read_bloom's `size - SIZEOF_U32` underflows (:78), or there
+ *                              is no trailer
+ *     TPZ_OPEN_BLOOM_RANGE     offset + 4 > size, offset = the BE u32 at size - 4 (:84: `size -
+ *                              SIZEOF_U32 - offset` underflows). size == offset + 4: no bloom
+ *                              section (:81-83); otherwise the filter is [offset, size - 4)
+ *     TPZ_OPEN_META_RANGE      offset < 4 (:94), or the BE u32 at offset - 4 is > offset - 4 (:97)
+ *     TPZ_OPEN_META_TRUNCATED  decode_block_meta's panics (:52-54): fewer than 6 bytes left for a
+ *                              record's offset and key length, or a key running past offset - 4.
+ *                              The reference decodes the whole section before anything looks at
+ *                              the offsets, so this wins over BAD_EXTENTS
+ *     TPZ_OPEN_BAD_EXTENTS     the block offsets followed by the meta offset are not
+ *                              non-decreasing (read_block's `end - offset`, :154-164)
+ *     TPZ_OPEN_NO_BLOCKS       an empty meta section (init_samllest_biggest_key's block_metas[0],
+ *                              :143-151)
+ *     TPZ_OPEN_UNSUPPORTED     not a reference outcome: len > 2^34 (this keeps n_blocks below
+ *                              2^32), or a span that breaks the rules above
+ *   d_file_block, d_file_key  n_files + 1 u64 each: exclusive prefix sums over the files of
+ *           n_blocks and of the first keys' bytes; only OK files count; the last element is the
+ *           total. The caller reads both totals back to size tpz_open_metas' outputs.
+ *   d_scratch  tpz_open_scratch_bytes(span_bytes, n_files) bytes, 8-byte aligned: one 16-byte
+ *           checkpoint per TPZ_OPEN_TILE bytes of every meta section, handed to tpz_open_metas.
+ *
+ * tpz_open_metas, for an OK file f with n blocks, b = d_file_block[f] + f:
+ *   d_ext[b + j], j = 0..n        the block offsets, then the meta offset, relative to the image's
+ *                                 first byte: block j is image[d_ext[b + j] .. d_ext[b + j + 1])
+ *   d_first_pos[b + j], j = 0..n  positions local to the file, starting at 0: block j's first key
+ *                                 is d_first_keys[d_file_key[f] + d_first_pos[b + j] ..
+ *                                 d_file_key[f] + d_first_pos[b + j + 1])
+ * so a tpz_table for file f is three pointer offsets into the shared arrays. d_info[8f + 7] bit 0
+ * is set when some block's last byte is tag 2 or 3 (compress.rs:104-111: the codec step is
+ * needed). Nothing is written at or past block_cap + n_files entries of d_ext / d_first_pos or
+ * key_cap bytes of d_first_keys; the caller passes the totals tpz_open_index reported.
+ *
+ * Both calls are asynchronous on `stream` and use no workspace but d_scratch.
+ * TPZ_ERR_INVALID_ARG, before any device work, for null pointers, misaligned pointers (u64 arrays
+ * and d_scratch 8-byte) or scratch_bytes < tpz_open_scratch_bytes(span_bytes, n_files).
+ * n_files == 0 is valid and does nothing. */
+#define TPZ_HAS_OPEN 1
+#define TPZ_OPEN_TILE 4096u /* bytes of meta section per checkpoint */
+#define TPZ_OPEN_OK 0
+#define TPZ_OPEN_SHORT 1
+#define TPZ_OPEN_BLOOM_RANGE 2
+#define TPZ_OPEN_META_RANGE 3
+#define TPZ_OPEN_META_TRUNCATED 4
+#define TPZ_OPEN_BAD_EXTENTS 5
+#define TPZ_OPEN_NO_BLOCKS 6
+#define TPZ_OPEN_UNSUPPORTED 7
+static inline uint64_t tpz_open_scratch_bytes(uint64_t span_bytes, uint64_t n_files) {
+  return (span_bytes / TPZ_OPEN_TILE + 2 * n_files) * 16;
+}
+tpz_err tpz_open_index(tpz_ctx* ctx, const uint8_t* d_src, uint64_t span_bytes,
+                       const uint64_t* d_span, uint32_t n_files, uint64_t* d_info,
+                       uint64_t* d_file_block, uint64_t* d_file_key, uint8_t* d_scratch,
+                       uint64_t scratch_bytes, void* stream);
+tpz_err tpz_open_metas(tpz_ctx* ctx, const uint8_t* d_src, uint64_t span_bytes,
+                       const uint64_t* d_span, uint32_t n_files, uint64_t* d_info,
+                       const uint64_t* d_file_block, const uint64_t* d_file_key,
+                       const uint8_t* d_scratch, uint64_t scratch_bytes, uint64_t* d_ext,
+                       uint64_t* d_first_pos, uint8_t* d_first_keys, uint64_t block_cap,
+                       uint64_t key_cap, void* stream);
+
 /* ---- host write side (inputs for benches and the table facade) ---------------------------
  * SsTableBuilder::add + block_build (src/table/builder.rs:49-85) with BlockBuilder's fill rule
  * (src/block/builder.rs:26-41) and Block::encode + Uncompress (src/block.rs:31-44,

@@ -97,6 +97,27 @@ pub const TPZ_WAL_END_IMAGE: u64 = 0;
 pub const TPZ_WAL_END_EMPTY_KEY: u64 = 1;
 pub const TPZ_WAL_TRUNCATED: u64 = 2;
 
+/// The header declares `tpz_open_index` / `tpz_open_metas` (additive within ABI 8): `SsTable::open`'s
+/// parse over file images that are resident in HBM.
+pub const TPZ_HAS_OPEN: u32 = 1;
+/// Bytes of meta section per checkpoint of `tpz_open_index`'s scratch.
+pub const TPZ_OPEN_TILE: u32 = 4096;
+/// `tpz_open_index`'s `d_info[8 f]`: the file's status, `SsTable::open`'s checks in order.
+pub const TPZ_OPEN_OK: u64 = 0;
+pub const TPZ_OPEN_SHORT: u64 = 1;
+pub const TPZ_OPEN_BLOOM_RANGE: u64 = 2;
+pub const TPZ_OPEN_META_RANGE: u64 = 3;
+pub const TPZ_OPEN_META_TRUNCATED: u64 = 4;
+pub const TPZ_OPEN_BAD_EXTENTS: u64 = 5;
+pub const TPZ_OPEN_NO_BLOCKS: u64 = 6;
+pub const TPZ_OPEN_UNSUPPORTED: u64 = 7;
+
+/// `tpz_open_scratch_bytes` (a static inline of the header): 16 bytes per tile of the span plus
+/// two tiles per file.
+pub const fn tpz_open_scratch_bytes(span_bytes: u64, n_files: u64) -> u64 {
+    (span_bytes / TPZ_OPEN_TILE as u64 + 2 * n_files) * 16
+}
+
 /// `tpz_batch`: blocks (or ranges, or files) back to back in HBM; block i is
 /// `d_src[d_ext[i] .. d_ext[i + 1])`.
 #[repr(C)]
@@ -416,6 +437,16 @@ extern "C" {
                           d_images: *const tpz_sst_image, n_images: u32, max_blocks: u32,
                           d_base: *mut u8, span_bytes: u64, d_info: *mut u64,
                           stream: *mut c_void) -> TpzErr;
+    pub fn tpz_open_index(ctx: *mut TpzCtx, d_src: *const u8, span_bytes: u64,
+                          d_span: *const u64, n_files: u32, d_info: *mut u64,
+                          d_file_block: *mut u64, d_file_key: *mut u64, d_scratch: *mut u8,
+                          scratch_bytes: u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_open_metas(ctx: *mut TpzCtx, d_src: *const u8, span_bytes: u64,
+                          d_span: *const u64, n_files: u32, d_info: *mut u64,
+                          d_file_block: *const u64, d_file_key: *const u64,
+                          d_scratch: *const u8, scratch_bytes: u64, d_ext: *mut u64,
+                          d_first_pos: *mut u64, d_first_keys: *mut u8, block_cap: u64,
+                          key_cap: u64, stream: *mut c_void) -> TpzErr;
     pub fn tpz_build_blocks(h_keys: *const u8, h_kpos: *const u64, h_vals: *const u8,
                             h_vpos: *const u64, n_entries: u64, block_size: u32, h_out: *mut u8,
                             out_cap: u64, h_ext: *mut u64, ext_cap: u64, n_blocks: *mut u64,

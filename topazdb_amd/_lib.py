@@ -42,6 +42,10 @@ MERGE_LANE_COPY_MAX = 256  # longer keys / values are copied by the whole wave (
 BLOOM_SLICE_BITS = 1 << 19  # bits per slice of tpz_bloom_build's partitioned path (csrc kBloomSliceBits)
 BLOOM_MAX_SLICES = 1024   # filters of more slices take the atomic kernel (csrc kBloomMaxSlices)
 BLOOM_WG_PROBES = 12288   # a workgroup takes BLOOM_WG_PROBES // k keys (csrc kBloomWgProbes)
+OPEN_TILE = 4096          # TPZ_OPEN_TILE: bytes of meta section per checkpoint of tpz_open_index
+# tpz_open_index's d_info[8f] (TPZ_OPEN_*)
+(OPEN_OK, OPEN_SHORT, OPEN_BLOOM_RANGE, OPEN_META_RANGE, OPEN_META_TRUNCATED, OPEN_BAD_EXTENTS,
+ OPEN_NO_BLOCKS, OPEN_UNSUPPORTED) = range(8)
 LDS_BLOCK_BYTES = 94192  # TPZ_LDS_BLOCK_BYTES: longer blocks with 64+ entries take the spill path
 BIGWAVE_BLOCK_BYTES = 0x40000000   # TPZ_BIGWAVE_BLOCK_BYTES
 
@@ -298,6 +302,15 @@ def lib() -> C.CDLL:
         L.tpz_wal_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32] + \
             [C.c_void_p] * 6
         L.tpz_wal_entries.restype = C.c_int
+        if not hasattr(L, "tpz_open_index"):      # (additive within ABI 8: an older build lacks it)
+            raise TpzError(f"{LIB_PATH} does not export tpz_open_index: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_open_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32] + \
+            [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p]
+        L.tpz_open_index.restype = C.c_int
+        L.tpz_open_metas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32] + \
+            [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint64, C.c_uint64, C.c_void_p]
+        L.tpz_open_metas.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -799,6 +812,29 @@ class Context:
                                    max_blocks, C.c_void_p(d_base), span_bytes, C.c_void_p(d_info),
                                    C.c_void_p(stream)), "tpz_sst_finish")
 
+    def open_index_ptrs(self, d_src: int, span_bytes: int, d_span: int, n_files: int, d_info: int,
+                        d_file_block: int, d_file_key: int, d_scratch: int, scratch_bytes: int,
+                        stream: int = 0) -> None:
+        """tpz_open_index: SsTable::open's footer checks and meta walk (table.rs:75-112) for
+        n_files resident file images; d_info: 8 u64 per file."""
+        check(lib().tpz_open_index(self.handle, C.c_void_p(d_src), span_bytes, C.c_void_p(d_span),
+                                   n_files, C.c_void_p(d_info), C.c_void_p(d_file_block),
+                                   C.c_void_p(d_file_key), C.c_void_p(d_scratch), scratch_bytes,
+                                   C.c_void_p(stream)), "tpz_open_index")
+
+    def open_metas_ptrs(self, d_src: int, span_bytes: int, d_span: int, n_files: int, d_info: int,
+                        d_file_block: int, d_file_key: int, d_scratch: int, scratch_bytes: int,
+                        d_ext: int, d_first_pos: int, d_first_keys: int, block_cap: int,
+                        key_cap: int, stream: int = 0) -> None:
+        """tpz_open_metas: every opened file's extents, first-key positions and first keys from
+        tpz_open_index's checkpoints, and the codec flag in d_info."""
+        check(lib().tpz_open_metas(self.handle, C.c_void_p(d_src), span_bytes, C.c_void_p(d_span),
+                                   n_files, C.c_void_p(d_info), C.c_void_p(d_file_block),
+                                   C.c_void_p(d_file_key), C.c_void_p(d_scratch), scratch_bytes,
+                                   C.c_void_p(d_ext), C.c_void_p(d_first_pos),
+                                   C.c_void_p(d_first_keys), block_cap, key_cap,
+                                   C.c_void_p(stream)), "tpz_open_metas")
+
     def flat_entry_pos_ptrs(self, cols: dict, n_blocks: int, d_kpos: int, d_vpos: int,
                             d_info: int, stream: int = 0) -> None:
         """tpz_flat_entry_pos: the flat columns' entry positions (cols maps FLAT_FIELDS -> pointer)."""
@@ -842,6 +878,11 @@ def bloom_geometry(n_keys: int, fpp: float):
 def sst_image_bytes(data_bytes: int, n_blocks: int, first_key_bytes: int, filter_len: int) -> int:
     """tpz_sst_image_bytes: the size of an SST file image (filter_len 0: no bloom section)."""
     return int(lib().tpz_sst_image_bytes(data_bytes, n_blocks, first_key_bytes, filter_len))
+
+
+def open_scratch_bytes(span_bytes: int, n_files: int) -> int:
+    """tpz_open_scratch_bytes: 16 bytes per TPZ_OPEN_TILE of the span plus two tiles per file."""
+    return (span_bytes // OPEN_TILE + 2 * n_files) * 16
 
 
 def xxh3_64(b: bytes) -> int:

@@ -481,3 +481,64 @@ def decompress_batch(ctx: Context, batch: DeviceBatch, stream: torch.cuda.Stream
         return decompress_batch(ctx, batch, stream, claimed=False)
     out = DeviceBatch(dst, ext, ctx.device)
     return out, st
+
+
+class OpenIndex:
+    """tpz_open_index's device outputs for a batch of resident file images: `span` (int64,
+    n_files x 2: start and length), `info` (int64, n_files x 8: TPZ_OPEN_* status, size, meta
+    offset, meta bytes, bloom offset or -1, filter_len, n_blocks, flags), `file_block` and
+    `file_key` (int64, n_files + 1: exclusive prefix sums of the opened files' blocks and first-key
+    bytes) and the checkpoints `scratch` that open_metas continues from."""
+
+    def __init__(self, src, span, span_bytes, info, file_block, file_key, scratch):
+        self.src, self.span, self.span_bytes = src, span, span_bytes
+        self.info, self.file_block, self.file_key, self.scratch = info, file_block, file_key, scratch
+        self.n_files = int(span.shape[0])
+
+
+def open_index(ctx: Context, src: torch.Tensor, spans, stream: torch.cuda.Stream | None = None
+               ) -> OpenIndex:
+    """tpz_open_index (asynchronous): SsTable::open's footer checks and meta walk
+    (src/table.rs:75-112) for the file images src[start : start + len] of `spans` ((start, len)
+    pairs in increasing order, or an int64 device tensor of them), each a whole file with its
+    CRC trailer."""
+    dev = _dev(ctx.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    assert src.dtype == torch.uint8 and src.is_cuda
+    if not isinstance(spans, torch.Tensor):
+        a = np.asarray(list(spans), np.uint64).reshape(-1, 2).view(np.int64)
+        spans = torch.from_numpy(a.copy()).to(dev)
+    n = int(spans.shape[0])
+    span_bytes = int(src.numel())
+    sb = _lib.open_scratch_bytes(span_bytes, n)
+    with torch.cuda.stream(s):
+        info = torch.empty((max(n, 1), 8), dtype=torch.int64, device=dev)
+        fb = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        fk = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(max(sb, 16), dtype=torch.uint8, device=dev)
+    if n:
+        ctx.open_index_ptrs(src.data_ptr(), span_bytes, spans.data_ptr(), n, info.data_ptr(),
+                            fb.data_ptr(), fk.data_ptr(), scratch.data_ptr(), sb, s.cuda_stream)
+    return OpenIndex(src, spans, span_bytes, info[:n], fb, fk, scratch)
+
+
+def open_metas(ctx: Context, idx: OpenIndex, n_blocks: int, key_bytes: int,
+               stream: torch.cuda.Stream | None = None):
+    """tpz_open_metas (asynchronous) with the totals open_index reported (file_block[-1],
+    file_key[-1]). Returns device tensors (ext, first_pos, first_keys): int64 n_blocks + n_files
+    entries each (file f's n + 1 entries start at file_block[f] + f) and the uint8 key bytes (file
+    f's at file_key[f]); open_index's info gains the codec flag."""
+    dev = _dev(ctx.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    n = idx.n_files
+    with torch.cuda.stream(s):
+        ext = torch.zeros(n_blocks + n + 1, dtype=torch.int64, device=dev)
+        pos = torch.zeros(n_blocks + n + 1, dtype=torch.int64, device=dev)
+        keys = torch.zeros(key_bytes + 1, dtype=torch.uint8, device=dev)
+    if n:
+        ctx.open_metas_ptrs(idx.src.data_ptr(), idx.span_bytes, idx.span.data_ptr(), n,
+                            idx.info.data_ptr(), idx.file_block.data_ptr(),
+                            idx.file_key.data_ptr(), idx.scratch.data_ptr(),
+                            _lib.open_scratch_bytes(idx.span_bytes, n), ext.data_ptr(),
+                            pos.data_ptr(), keys.data_ptr(), n_blocks, key_bytes, s.cuda_stream)
+    return ext, pos, keys

@@ -34,7 +34,7 @@ from ._lib import Context
 from .batch import DeviceBatch, FlatColumns, decode_flat, decompress_batch
 from .encode import (DeviceEntries, EntryError, compress_blocks, compress_bound, encode_blocks_async,
                      encode_bound, plan_blocks_async)
-from .table import BlockError, ReferencePanic
+from .table import BlockError, ReferencePanic, open_images
 
 
 def _dev(device: int) -> torch.device:
@@ -177,6 +177,23 @@ class TaskTables(list):
     count, block bound and span tpz_sst_finish ran with; tools/tables_probe.py times it again)."""
     arena: torch.Tensor
     entries: DeviceEntries
+
+    def open(self, ctx: Context, verify: bool = False, strict: bool = True) -> list:
+        """The task's output tables as resident DeviceTables, in this list's order, opened where
+        their images lie (table.open_images: no D2H, host parse or upload); ready for
+        DeviceLevels(ctx, levels) / DeviceLsm. verify: the whole-file CRC check first (the images
+        were written by this process: off by default)."""
+        if not len(self):
+            return []
+        base = self.arena.data_ptr()
+        order = sorted(range(len(self)), key=lambda i: self[i].image.data_ptr())
+        got = open_images(ctx, self.arena,
+                          [(self[i].image.data_ptr() - base, self[i].size) for i in order],
+                          verify, strict)
+        out = [None] * len(self)
+        for i, t in zip(order, got):
+            out[i] = t
+        return out
 
 
 def _bound_lower(lower) -> bytes:
@@ -473,6 +490,12 @@ def _flush_runs(ctx: Context, runs, block_size: int, codec: int, false_positive_
     t = OutputTable(arena[:size], size, int(g[1]), None if boff == 2**64 - 1 else boff, nb, 0,
                     n_out)
     return t, merged
+
+
+def open_output(ctx: Context, table, verify: bool = False):
+    """flush_runs' OutputTable as a resident DeviceTable, opened where its image lies
+    (table.open_images); the L0 table a flush just wrote goes straight into DeviceLsm."""
+    return open_images(ctx, table.image, [(0, table.size)], verify)[0]
 
 
 def flush_like_start_flush(ctx: Context, view, block_size: int = 4096, codec: int = 1,

@@ -1719,6 +1719,79 @@ tpz_err tpz_sst_finish(tpz_ctx* c, const tpz_entries* en, const tpz_sst_image* d
   return TPZ_SUCCESS;
 }
 
+static bool open_args_ok(const tpz_ctx* c, const uint8_t* d_src, const uint64_t* d_span,
+                         uint32_t n_files, const uint64_t* d_info, const uint64_t* d_file_block,
+                         const uint64_t* d_file_key, const uint8_t* d_scratch,
+                         uint64_t scratch_bytes, uint64_t span_bytes) {
+  if (!c || !d_src || !d_span || !d_info || !d_file_block || !d_file_key || !d_scratch)
+    return false;
+  if (((uintptr_t)d_span | (uintptr_t)d_info | (uintptr_t)d_file_block | (uintptr_t)d_file_key |
+       (uintptr_t)d_scratch) & 7u)
+    return false;
+  return n_files <= 0x7FFFFFFFu && scratch_bytes >= tpz_open_scratch_bytes(span_bytes, n_files);
+}
+
+tpz_err tpz_open_index(tpz_ctx* c, const uint8_t* d_src, uint64_t span_bytes,
+                       const uint64_t* d_span, uint32_t n_files, uint64_t* d_info,
+                       uint64_t* d_file_block, uint64_t* d_file_key, uint8_t* d_scratch,
+                       uint64_t scratch_bytes, void* stream) {
+  if (!open_args_ok(c, d_src, d_span, n_files, d_info, d_file_block, d_file_key, d_scratch,
+                    scratch_bytes, span_bytes))
+    return TPZ_ERR_INVALID_ARG;
+  if (n_files == 0) return TPZ_SUCCESS;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  tpz::OpenIndexLaunch a{};
+  a.src = d_src;
+  a.span_bytes = span_bytes;
+  a.span = d_span;
+  a.n_files = n_files;
+  a.info = d_info;
+  a.file_block = d_file_block;
+  a.file_key = d_file_key;
+  a.ck = reinterpret_cast<uint64_t*>(d_scratch);
+  a.n_ck = tpz_open_scratch_bytes(span_bytes, n_files) / 16;
+  // a tile no record starts in keeps the fill: tpz_open_metas skips it
+  TPZ_HIP(hipMemsetAsync(d_scratch, 0xFF, (size_t)a.n_ck * 16, s));
+  tpz::launch_open_index(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_open_metas(tpz_ctx* c, const uint8_t* d_src, uint64_t span_bytes,
+                       const uint64_t* d_span, uint32_t n_files, uint64_t* d_info,
+                       const uint64_t* d_file_block, const uint64_t* d_file_key,
+                       const uint8_t* d_scratch, uint64_t scratch_bytes, uint64_t* d_ext,
+                       uint64_t* d_first_pos, uint8_t* d_first_keys, uint64_t block_cap,
+                       uint64_t key_cap, void* stream) {
+  if (!open_args_ok(c, d_src, d_span, n_files, d_info, d_file_block, d_file_key, d_scratch,
+                    scratch_bytes, span_bytes))
+    return TPZ_ERR_INVALID_ARG;
+  if (!d_ext || !d_first_pos || !d_first_keys || (((uintptr_t)d_ext | (uintptr_t)d_first_pos) & 7u))
+    return TPZ_ERR_INVALID_ARG;
+  if (block_cap > ~0ull - n_files) return TPZ_ERR_INVALID_ARG;
+  if (n_files == 0) return TPZ_SUCCESS;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::OpenIndexLaunch a{};
+  a.src = d_src;
+  a.span_bytes = span_bytes;
+  a.span = d_span;
+  a.n_files = n_files;
+  a.info = d_info;
+  a.file_block = const_cast<uint64_t*>(d_file_block);
+  a.file_key = const_cast<uint64_t*>(d_file_key);
+  a.ck = reinterpret_cast<uint64_t*>(const_cast<uint8_t*>(d_scratch));
+  a.n_ck = tpz_open_scratch_bytes(span_bytes, n_files) / 16;
+  a.ext = d_ext;
+  a.first_pos = d_first_pos;
+  a.first_keys = d_first_keys;
+  a.block_cap = block_cap;
+  a.key_cap = key_cap;
+  tpz::launch_open_metas(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
 uint64_t tpz_host_xxh3_64(const uint8_t* h_buf, uint64_t len) {
   return tpz::xxh3::hash64(h_buf, len);
 }

@@ -551,6 +551,30 @@ uint32_t finish_parts(uint32_t max_blocks);
 void launch_finish_layout(const FinishLaunch& a, hipStream_t stream);
 void launch_finish_crc(const FinishLaunch& a, hipStream_t stream);
 
+// tpz_open_index / tpz_open_metas (tpz_open.hip): SsTable::open's parse over resident file
+// images. launch_open_index: the footer checks, the walk of every meta section with its
+// checkpoints (ck, filled with 0xFF by the caller), the prefix sums over the files; the output
+// fields are unused. launch_open_metas: extents, first keys and positions from the checkpoints,
+// then the codec flags.
+struct OpenIndexLaunch {
+  const uint8_t* src;
+  uint64_t span_bytes;
+  const uint64_t* span;         // {start, len} per file
+  uint32_t n_files;             // 1 .. 2^31 - 1 (a grid dimension)
+  uint64_t* info;               // 8 u64 per file
+  uint64_t* file_block;         // n_files + 1
+  uint64_t* file_key;           // n_files + 1
+  uint64_t* ck;                 // n_ck checkpoints of 2 u64
+  uint64_t n_ck;
+  uint64_t* ext;
+  uint64_t* first_pos;
+  uint8_t* first_keys;
+  uint64_t block_cap;
+  uint64_t key_cap;
+};
+void launch_open_index(const OpenIndexLaunch& a, hipStream_t stream);
+void launch_open_metas(const OpenIndexLaunch& a, hipStream_t stream);
+
 // tpz_compress_blocks (tpz_compress.hip): scratch bytes for the per-block slots; the snappy
 // encode, the scan of the sizes into dst_ext and the packing into dst.
 uint64_t compress_scratch_bytes(uint64_t src_bytes, uint32_t n_blocks);

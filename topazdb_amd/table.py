@@ -10,6 +10,8 @@ Same names, argument meaning and error behaviour as the reference:
   BlockIterator     src/block/iterator.rs:9-110
   SsTableIterator   src/table/iterator.rs:10-96
   Bloom.may_contain src/bloom.rs:72-84 (host; the filter is not on the decode path)
+  open_images       src/table.rs:91-112 for file images that already lie in HBM (the parse on
+                    the device, tpz_open_index / tpz_open_metas; the decode in place)
 
 Errors: where the reference returns an anyhow::Error, this raises BlockError whose text is the
 reference's message ("checksum: expected E, actual A", "data is empty", "invaild data"); where
@@ -31,7 +33,8 @@ import torch
 from . import _lib
 from ._lib import (BLOCK_BAD_ENTRY, BLOCK_BAD_TAG, BLOCK_CHECKSUM_MISMATCH, BLOCK_EMPTY,
                    BLOCK_MALFORMED, BLOCK_OK, ENTRY_BAD_KEY, ENTRY_BAD_VALUE, ENTRY_OK, Context)
-from .batch import DeviceBatch, decode_batch, decompress_batch, exact_columns, verify_files
+from .batch import (DeviceBatch, decode_batch, decompress_batch, exact_columns, open_index,
+                    open_metas, verify_files)
 
 CHECKSUM_SIZE = 4  # src/checksum.rs:4
 SIZEOF_U16 = 2
@@ -188,26 +191,81 @@ class DeviceTable:
         dev = torch.device("cuda", ctx.device)
         src = np.frombuffer(region, np.uint8) if region else np.zeros(0, np.uint8)
         batch = DeviceBatch(src, ext, ctx.device)
-        nb = self.n_blocks = batch.n_blocks
-        self.codec = None
-        if any(int(ext[b + 1]) > int(ext[b]) and region[int(ext[b + 1]) - 1] in (2, 3)
-               for b in range(nb)):
-            batch, st = decompress_batch(ctx, batch)
-            self.codec = st[:nb]
-        self.batch = batch
-        # complete(): blocks that spilled into a too-small arena are decoded again with room
-        cols = exact_columns(ctx, batch) if exact_ends else None
-        self.cols = decode_batch(ctx, batch, cols).complete()
-        # the status a reader of block i sees: the codec's Err wins over the decode of its stub
-        self.status = self.cols.status[:max(nb, 1)].clone()
-        if self.codec is not None:
-            self.status[:nb] = torch.where(self.codec != BLOCK_OK, self.codec, self.status[:nb])
+        nb = batch.n_blocks
+        self._decode(batch, any(int(ext[b + 1]) > int(ext[b]) and
+                                region[int(ext[b + 1]) - 1] in (2, 3) for b in range(nb)),
+                     exact_ends)
         fk, fpos = _pack(first_keys or [])
         self.first_keys = torch.from_numpy(fk.copy()).to(dev)
         self.first_pos = torch.from_numpy(fpos).to(dev)
         self.bloom = None if bloom is None else torch.from_numpy(
             np.frombuffer(bloom or b"\0", np.uint8).copy()).to(dev)
         self.bloom_len = 0 if bloom is None else len(bloom)
+
+    def _decode(self, batch: DeviceBatch, has_codec: bool, exact_ends: bool) -> None:
+        """The codec step where some block needs it, then one tpz_decode_blocks launch."""
+        nb = self.n_blocks = batch.n_blocks
+        self.codec = None
+        if has_codec:
+            batch, st = decompress_batch(self.ctx, batch)
+            self.codec = st[:nb]
+        self.batch = batch
+        # complete(): blocks that spilled into a too-small arena are decoded again with room
+        cols = exact_columns(self.ctx, batch) if exact_ends else None
+        self.cols = decode_batch(self.ctx, batch, cols).complete()
+        # the status a reader of block i sees: the codec's Err wins over the decode of its stub
+        self.status = self.cols.status[:max(nb, 1)].clone()
+        if self.codec is not None:
+            self.status[:nb] = torch.where(self.codec != BLOCK_OK, self.codec, self.status[:nb])
+
+    @classmethod
+    def from_resident(cls, ctx: Context, image: torch.Tensor, ext: torch.Tensor,
+                      first_keys: torch.Tensor, first_pos: torch.Tensor,
+                      filter_view: torch.Tensor | None, filter_len: int,
+                      has_codec: bool) -> "DeviceTable":
+        """The same object over a file image that already lies in HBM (open_images): `image` is
+        the file (a uint8 device tensor whose first byte is 16-byte aligned, the decode's d_src
+        rule), `ext` its n + 1 block extents, `first_keys` / `first_pos` the block first keys with
+        their n + 1 positions, `filter_view` the bloom filter where it lies in the image (None:
+        no bloom section); all device tensors, as tpz_open_metas leaves them. The data region is
+        decoded in place; nothing is uploaded. has_codec: some block is snappy or lz4 (the
+        flag tpz_open_metas reports), so the codec step runs first."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._decode(DeviceBatch(image, ext, ctx.device), has_codec, True)
+        self.first_keys, self.first_pos = first_keys, first_pos
+        self.bloom = filter_view
+        self.bloom_len = 0 if filter_view is None else int(filter_len)
+        return self
+
+    def last_key(self) -> bytes:
+        """init_samllest_biggest_key's biggest key (table.rs:145-149): the last entry of the last
+        block, read back from that block's count and ends alone when its status is plain OK;
+        another status goes through host_blocks(). Raises what the reference does there."""
+        b = self.n_blocks - 1
+        if b < 0:
+            raise ReferencePanic("index out of bounds: the len is 0 but the index is 0")
+        c = self.cols
+        if int(self.status[b].cpu()) != BLOCK_OK or c.entry_first is None:
+            r = self.host_blocks()[b]
+            if isinstance(r, Exception):
+                raise r
+            it = BlockIterator.create_and_seek_to_first(r)
+            it.seek_to_last()
+            if not it.is_valid():
+                raise ReferencePanic("assertion failed: iter.is_valid()")
+            return it.key()
+        n = int(c.count[b].cpu()) & 0xFFFFFFFF
+        if n == 0:          # offsets.len() - 1 underflows (iterator.rs:60)
+            raise ReferencePanic("attempt to subtract with overflow")
+        pair = int(c.entry_first[b].cpu()) + n - 1
+        ke = int(c.ends[2 * pair].cpu()) & 0xFFFFFFFF
+        ks = (int(c.ends[2 * pair - 2].cpu()) & 0xFFFFFFFF) if n > 1 else 0
+        base = int(_lib.slot_base(int(self.batch.ext_host[b]), b))
+        key = c.data[base + ks:base + ke].cpu().numpy().tobytes()
+        if not key:
+            raise ReferencePanic("assertion failed: iter.is_valid()")
+        return key
 
     def table(self) -> _lib.Table:
         c = self.cols
@@ -641,6 +699,107 @@ class SsTable:
 
     def num_of_blocks(self) -> int:
         return len(self.block_metas)
+
+
+def _open_error(status: int, image: torch.Tensor) -> Exception:
+    """The exception SsTable.open raises for a file tpz_open_index gave `status` (TPZ_OPEN_*)."""
+    if status in (_lib.OPEN_SHORT, _lib.OPEN_BLOOM_RANGE, _lib.OPEN_META_RANGE):
+        return ReferencePanic("attempt to subtract with overflow")
+    if status == _lib.OPEN_BAD_EXTENTS:
+        return ReferencePanic("range start index out of range")
+    if status == _lib.OPEN_NO_BLOCKS:
+        return ReferencePanic("index out of bounds: the len is 0 but the index is 0")
+    if status == _lib.OPEN_META_TRUNCATED:
+        # decode_block_meta panics in get_u32 / get_u16 or in copy_to_bytes, with different
+        # texts; the status is one class, so the failed file's meta section is decoded again on
+        # the host for the text (the error path only)
+        data = image.cpu().numpy().tobytes()
+        size = len(data) - CHECKSUM_SIZE
+        offset = _be32(data[size - 4:size])
+        meta_offset = _be32(data[offset - 4:offset])
+        try:
+            BlockMeta.decode_block_meta(data[meta_offset:offset - 4])
+        except ReferencePanic as e:
+            return e
+    return ValueError(f"tpz_open_index: status {status} (an image longer than 2^34 bytes, or "
+                      "spans out of order)")
+
+
+def open_images(ctx: Context, arena: torch.Tensor, spans, verify: bool = True,
+                strict: bool = True) -> list:
+    """SsTable::open (src/table.rs:91-112) for SST file images that already lie in HBM, without a
+    host round trip: image i is arena[start : start + length] for (start, length) = spans[i], the
+    whole file with its CRC trailer, as compact_task and flush_runs leave them. Starts are
+    multiples of 16 (the decode's d_src alignment; ValueError otherwise), in increasing order,
+    and the images do not overlap.
+
+    verify: FileObject::open's whole-file check first, one tpz_verify_files over the images. Then
+    one tpz_open_index, one read-back of its totals and d_info, one tpz_open_metas, and per opened
+    table its decode in place (DeviceTable.from_resident). Returns per file its DeviceTable, with
+    `smallest_key`, `biggest_key` (init_samllest_biggest_key, :143-151), `size` and
+    `block_meta_offset` set; the tables keep the arena and the shared arrays alive. A file that
+    fails becomes the exception SsTable.open / FileObject.open raise for it: raised, the first in
+    file order, when `strict`; returned in its place otherwise."""
+    spans = [(int(s), int(n)) for s, n in spans]
+    end = 0
+    for s, n in spans:
+        if s % 16 or arena.data_ptr() % 16:
+            raise ValueError(f"image start {s} is not 16-byte aligned")
+        if s < end or n < 0 or s + n > arena.numel():
+            raise ValueError("spans must be in increasing order, disjoint and inside the arena")
+        end = s + n
+    nf = len(spans)
+    if nf == 0:
+        return []
+    dev = torch.device("cuda", ctx.device)
+    out: list = [None] * nf
+    if verify:
+        # images and the gaps between them as ranges 2i / 2i + 1 of one batch
+        ext = np.array([x for s, n in spans for x in (s, s + n)], np.uint64)
+        crc, st = verify_files(ctx, DeviceBatch(arena, ext, ctx.device))
+        crc = crc[:2 * nf - 1].cpu().numpy().view(np.uint32)
+        st = st[:2 * nf - 1].cpu().numpy()
+        for i, (s, n) in enumerate(spans):
+            if st[2 * i] == BLOCK_MALFORMED:
+                out[i] = ReferencePanic(f"image {i}: file shorter than its checksum")
+            elif st[2 * i] != BLOCK_OK:
+                expected = _be32(arena[s + n - 4:s + n].cpu().numpy().tobytes())
+                out[i] = _status_error(int(st[2 * i]), expected, int(crc[2 * i]))
+            if strict and out[i] is not None:
+                raise out[i]
+    idx = open_index(ctx, arena, spans)
+    info = idx.info.cpu().numpy().view(np.uint64)          # (waits for the stream)
+    fb = idx.file_block.cpu().numpy()
+    fk = idx.file_key.cpu().numpy()
+    ext, pos, keys = open_metas(ctx, idx, int(fb[-1]), int(fk[-1]))
+    flags = idx.info[:, 7].cpu().numpy()
+    for i, (s, n) in enumerate(spans):
+        if out[i] is not None:
+            continue
+        row = info[i]
+        image = arena[s:s + n]
+        if int(row[0]) != _lib.OPEN_OK:
+            out[i] = _open_error(int(row[0]), image)
+        else:
+            nb, b0, k0, k1 = int(row[6]), int(fb[i]) + i, int(fk[i]), int(fk[i + 1])
+            boff, flen = int(row[4]), int(row[5])
+            try:
+                t = DeviceTable.from_resident(
+                    ctx, image, ext[b0:b0 + nb + 1], keys[k0:max(k1, k0 + 1)],
+                    pos[b0:b0 + nb + 1],
+                    None if boff == 2**64 - 1 else image[boff:boff + flen], flen,
+                    bool(int(flags[i]) & 1))
+                t.arena = arena
+                t.size, t.block_meta_offset = int(row[1]), int(row[2])
+                p = pos[b0:b0 + 2].cpu().numpy()
+                t.smallest_key = keys[k0 + int(p[0]):k0 + int(p[1])].cpu().numpy().tobytes()
+                t.biggest_key = t.last_key()
+                out[i] = t
+            except (ReferencePanic, BlockError) as e:
+                out[i] = e
+        if strict and isinstance(out[i], Exception):
+            raise out[i]
+    return out
 
 
 class SsTableIterator:
