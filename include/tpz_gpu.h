@@ -504,7 +504,8 @@ tpz_err tpz_verify_files_flat_layout(tpz_ctx* ctx, const tpz_batch* blocks,
  *      own length for any other block. No size limit: blocks past the LDS windows are
  *      decompressed straight from HBM to HBM.
  *   2. the caller forms d_dst_ext = exclusive prefix sums of d_size (n_blocks + 1 entries) and
- *      allocates d_dst (d_dst_ext[n] bytes).
+ *      allocates d_dst (d_dst_ext[n] bytes). d_dst_ext[0] may be any position (the blocks then
+ *      follow other data in d_dst); every position is 64-bit, as in tpz_batch.
  *   3. tpz_decompress_blocks writes block i's uncompressed form to d_dst[d_dst_ext[i] ..
  *      d_dst_ext[i+1]) (other tags are copied unchanged) and d_status[i] = TPZ_BLOCK_OK,
  *      or TPZ_BLOCK_CODEC_ERROR (the codec's Err). A failed block's range

@@ -773,8 +773,11 @@ __device__ __forceinline__ bool codec_block(const CodecParams& p, u32 b, const B
 }
 
 __device__ __forceinline__ u64 readlane64(u64 x, u32 k) {
-  return ((u64)__builtin_amdgcn_readlane((u32)(x >> 32), k) << 32) |
-         __builtin_amdgcn_readlane((u32)x, k);
+  // (the builtin returns int: the halves go through u32, or a low half of 2^31 and more is
+  // sign-extended into the high one)
+  const u32 lo = __builtin_amdgcn_readlane((u32)x, k);
+  const u32 hi = __builtin_amdgcn_readlane((u32)(x >> 32), k);
+  return ((u64)hi << 32) | lo;
 }
 
 // Each wave takes blocks wave0, wave0 + S, wave0 + 2S, ... (S = waves in the grid); their
