@@ -1331,6 +1331,69 @@ tpz_err tpz_open_metas(tpz_ctx* ctx, const uint8_t* d_src, uint64_t span_bytes,
                        uint64_t* d_first_pos, uint8_t* d_first_keys, uint64_t block_cap,
                        uint64_t key_cap, void* stream);
 
+/* ---- resident tables as merge runs --------------------------------------------------------
+ * The device's SsTableIterator (src/table/iterator.rs:10-96) over tables whose decoded columns
+ * already lie in HBM behind tpz_table descriptors: for a list of tables in priority order
+ * (sub_compact's this_tables + next_tables, src/level.rs:184-197: an earlier table wins a key) the
+ * entries of every table, block after block, as one tpz_entries holding a run per table: dense key
+ * and value columns plus absolute entry positions, what tpz_merge_runs and the write side take.
+ * A compaction's inputs then come from the columns that serve the gets, with no host
+ * concatenation, upload or second decode. Additive within ABI 8: new symbols only
+ * (TPZ_HAS_TABLE_RUNS tells a consumer the header has them).
+ *
+ * d_tables: n_runs <= TPZ_MERGE_MAX_RUNS descriptors in device memory, in run order. h_block_first
+ * (host, n_runs + 1 u32, read during the call) starts at 0 and is non-decreasing; B =
+ * h_block_first[n_runs]. Run r is the blocks [h_block_first[r], h_block_first[r + 1]) of table r,
+ * counted from the table's block 0, in block order. A table may have no blocks; n_runs == 0 is
+ * valid and gives all totals 0.
+ *
+ * tpz_table_runs_layout (the sizing pass), with g = h_block_first[r] + b for block b of run r:
+ *   d_block_first  3 x (B + 1) u64: d_block_first[g] = the entries before block g in run order,
+ *           d_block_first[B + 1 + g] the key bytes, d_block_first[2 (B + 1) + g] the value bytes;
+ *           the totals at g = B. A block counts its n entries and its K key and V value bytes (the
+ *           last {kend, vend} pair) when its status is TPZ_BLOCK_OK or TPZ_BLOCK_OK_SPILLED; a
+ *           block of any other status (BAD_ENTRY, CHECKSUM_MISMATCH, CODEC_ERROR, MALFORMED, EMPTY,
+ *           BAD_TAG, SPILL_FULL), and a block past its descriptor's n_blocks, holds nothing. The
+ *           ends of a block with count 0 are not read.
+ *   d_run_first    n_runs + 1 u32: the entries before every run, tpz_merge_runs' h_run_first once
+ *           read back (saturated at UINT32_MAX).
+ *   d_info  4 u64: {entries, key bytes, value bytes, first bad block}. The entry count is a true
+ *           u64: the caller refuses 2^32 or more, tpz_entries.n_entries being u32. d_info[3] =
+ *           run << 32 | block of the first block in run order that holds nothing for its status,
+ *           or UINT64_MAX; the other outputs are as defined above either way (sub_compact's `?`
+ *           fails the compaction at that block: the caller decides).
+ *   Uses the stream's grow-only workspace for the scans' partial sums.
+ *
+ * tpz_table_runs_entries (the gather pass), over the same tables and d_block_first:
+ *   d_keys / d_vals  block g's K key bytes at d_keys[kb ..], kb = d_block_first[B + 1 + g], and its
+ *           V value bytes at d_vals[vb ..]: two byte-range copies per block out of its slot or its
+ *           spill record (one wave per block, 16-byte stores, the pieces a range shares with its
+ *           neighbours byte by byte: no two blocks store the same byte).
+ *   d_kpos / d_vpos  entry_cap + 1 u64 each: entry j of block g is e = d_block_first[g] + j,
+ *           d_kpos[e] = kb + (j ? kend[j - 1] : 0), d_vpos likewise; d_kpos[n] / d_vpos[n] = the
+ *           totals (n = d_info[0]), so (d_keys, d_kpos, d_vals, d_vpos, n, key bytes, value bytes)
+ *           is a tpz_entries and d_run_first its run table.
+ *   Nothing is written at or past key_cap / val_cap bytes, nor past index entry_cap of d_kpos /
+ *   d_vpos; a caller passes the totals of d_info. Empty keys are tpz_merge_runs' business.
+ * All position arithmetic is u64 (slot bases and spill offsets pass 2^32 for tables over 4 GiB).
+ * Every index read from device memory is clamped (n to the block's reserved pairs, K and V to the
+ * slot, an entry's end to K / V, a block to what the layout reserved), so tables whose columns
+ * were overwritten give wrong entries, not stray accesses outside the slot or the outputs.
+ *
+ * Both calls are asynchronous on `stream`. TPZ_ERR_INVALID_ARG, before any device work, for null
+ * pointers (d_keys / d_vals may be NULL with a capacity of 0, d_tables with n_runs 0), misaligned
+ * pointers (d_keys / d_vals 16-byte; d_tables and the u64 arrays 8-byte; d_run_first 4-byte), an
+ * h_block_first that does not start at 0 or decreases, or n_runs > TPZ_MERGE_MAX_RUNS. */
+#define TPZ_HAS_TABLE_RUNS 1
+tpz_err tpz_table_runs_layout(tpz_ctx* ctx, const tpz_table* d_tables, uint32_t n_runs,
+                              const uint32_t* h_block_first, uint64_t* d_block_first,
+                              uint32_t* d_run_first, uint64_t* d_info, void* stream);
+tpz_err tpz_table_runs_entries(tpz_ctx* ctx, const tpz_table* d_tables, uint32_t n_runs,
+                               const uint32_t* h_block_first, const uint64_t* d_block_first,
+                               uint8_t* d_keys, uint64_t key_cap, uint64_t* d_kpos,
+                               uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
+                               uint64_t entry_cap, void* stream);
+
 /* ---- host write side (inputs for benches and the table facade) ---------------------------
  * SsTableBuilder::add + block_build (src/table/builder.rs:49-85) with BlockBuilder's fill rule
  * (src/block/builder.rs:26-41) and Block::encode + Uncompress (src/block.rs:31-44,

@@ -112,6 +112,10 @@ pub const TPZ_OPEN_BAD_EXTENTS: u64 = 5;
 pub const TPZ_OPEN_NO_BLOCKS: u64 = 6;
 pub const TPZ_OPEN_UNSUPPORTED: u64 = 7;
 
+/// The header declares `tpz_table_runs_layout` / `tpz_table_runs_entries` (additive within ABI 8):
+/// resident tables gathered into the runs `tpz_merge_runs` takes.
+pub const TPZ_HAS_TABLE_RUNS: u32 = 1;
+
 /// `tpz_open_scratch_bytes` (a static inline of the header): 16 bytes per tile of the span plus
 /// two tiles per file.
 pub const fn tpz_open_scratch_bytes(span_bytes: u64, n_files: u64) -> u64 {
@@ -447,6 +451,15 @@ extern "C" {
                           d_scratch: *const u8, scratch_bytes: u64, d_ext: *mut u64,
                           d_first_pos: *mut u64, d_first_keys: *mut u8, block_cap: u64,
                           key_cap: u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_table_runs_layout(ctx: *mut TpzCtx, d_tables: *const TpzTable, n_runs: u32,
+                                 h_block_first: *const u32, d_block_first: *mut u64,
+                                 d_run_first: *mut u32, d_info: *mut u64,
+                                 stream: *mut c_void) -> TpzErr;
+    pub fn tpz_table_runs_entries(ctx: *mut TpzCtx, d_tables: *const TpzTable, n_runs: u32,
+                                  h_block_first: *const u32, d_block_first: *const u64,
+                                  d_keys: *mut u8, key_cap: u64, d_kpos: *mut u64,
+                                  d_vals: *mut u8, val_cap: u64, d_vpos: *mut u64,
+                                  entry_cap: u64, stream: *mut c_void) -> TpzErr;
     pub fn tpz_build_blocks(h_keys: *const u8, h_kpos: *const u64, h_vals: *const u8,
                             h_vpos: *const u64, n_entries: u64, block_size: u32, h_out: *mut u8,
                             out_cap: u64, h_ext: *mut u64, ext_cap: u64, n_blocks: *mut u64,

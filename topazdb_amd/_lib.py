@@ -311,6 +311,20 @@ def lib() -> C.CDLL:
         L.tpz_open_metas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32] + \
             [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint64, C.c_uint64, C.c_void_p]
         L.tpz_open_metas.restype = C.c_int
+        if not hasattr(L, "tpz_table_runs_layout"):   # (additive within ABI 8: an older build lacks it)
+            raise TpzError(f"{LIB_PATH} does not export tpz_table_runs_layout: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_table_runs_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+        L.tpz_table_runs_layout.restype = C.c_int
+        L.tpz_table_runs_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                             C.c_void_p]
+        L.tpz_table_runs_entries.restype = C.c_int
+        if hasattr(L, "tpz_debug_table_runs_entries"):   # diagnostic (not in tpz_gpu.h): runs_probe.py
+            L.tpz_debug_table_runs_entries.argtypes = \
+                list(L.tpz_table_runs_entries.argtypes[:-1]) + [C.c_uint32, C.c_void_p]
+            L.tpz_debug_table_runs_entries.restype = C.c_int
         L.tpz_bloom_geometry.argtypes = [C.c_uint64, C.c_double, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]
         L.tpz_bloom_geometry.restype = C.c_int
@@ -834,6 +848,34 @@ class Context:
                                    C.c_void_p(d_ext), C.c_void_p(d_first_pos),
                                    C.c_void_p(d_first_keys), block_cap, key_cap,
                                    C.c_void_p(stream)), "tpz_open_metas")
+
+    def table_runs_layout_ptrs(self, d_tables: int, n_runs: int, h_block_first: int,
+                               d_block_first: int, d_run_first: int, d_info: int,
+                               stream: int = 0) -> None:
+        """tpz_table_runs_layout: the entries, key bytes and value bytes before every block of
+        n_runs resident tables (Table descriptors in device memory) in run order, the run table
+        and the totals; d_info: 4 u64."""
+        check(lib().tpz_table_runs_layout(self.handle, C.c_void_p(d_tables), n_runs,
+                                          C.c_void_p(h_block_first), C.c_void_p(d_block_first),
+                                          C.c_void_p(d_run_first), C.c_void_p(d_info),
+                                          C.c_void_p(stream)), "tpz_table_runs_layout")
+
+    def table_runs_entries_ptrs(self, d_tables: int, n_runs: int, h_block_first: int,
+                                d_block_first: int, d_keys: int, key_cap: int, d_kpos: int,
+                                d_vals: int, val_cap: int, d_vpos: int, entry_cap: int,
+                                stream: int = 0, aligned: int | None = None) -> None:
+        """tpz_table_runs_entries: the tables' keys, values and entry positions gathered into one
+        tpz_entries, a run per table. aligned (0 / 1): the diagnostic export with the gather's
+        form chosen (1: aligned loads and a funnel shift; 0: the product's wave_copy;
+        tools/runs_probe.py)."""
+        args = (self.handle, C.c_void_p(d_tables), n_runs, C.c_void_p(h_block_first),
+                C.c_void_p(d_block_first), C.c_void_p(d_keys), key_cap, C.c_void_p(d_kpos),
+                C.c_void_p(d_vals), val_cap, C.c_void_p(d_vpos), entry_cap)
+        if aligned is None:
+            check(lib().tpz_table_runs_entries(*args, C.c_void_p(stream)), "tpz_table_runs_entries")
+        else:
+            check(lib().tpz_debug_table_runs_entries(*args, int(aligned), C.c_void_p(stream)),
+                  "tpz_debug_table_runs_entries")
 
     def flat_entry_pos_ptrs(self, cols: dict, n_blocks: int, d_kpos: int, d_vpos: int,
                             d_info: int, stream: int = 0) -> None:

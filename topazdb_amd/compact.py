@@ -7,7 +7,9 @@ the inputs' entries as flat columns, `entries_from_flat` (tpz_flat_entry_pos) tu
 the write side's tpz_entries, `merge_runs` (tpz_merge_runs) merges the tables' runs with the
 iterator's tie rule, and the write side (tpz_plan_blocks_async, tpz_encode_blocks_async,
 tpz_compress_blocks) writes the output blocks. Tombstones (empty values) are kept: only
-LsmIterator drops them, and compaction does not use it.
+LsmIterator drops them, and compaction does not use it. Input tables that are already resident as
+DeviceTables skip the read side: `entries_from_tables` (tpz_table_runs_layout,
+tpz_table_runs_entries) gathers their decoded columns into the runs the merge takes.
 
 `compact_task` is do_compact (src/level.rs:133-222) around that: the sub-compactions' key ranges
 over the merged entries (tpz_entries_bound), SsTableBuilder's table cuts (tpz_table_cut) and every
@@ -34,7 +36,7 @@ from ._lib import Context
 from .batch import DeviceBatch, FlatColumns, decode_flat, decompress_batch
 from .encode import (DeviceEntries, EntryError, compress_blocks, compress_bound, encode_blocks_async,
                      encode_bound, plan_blocks_async)
-from .table import BlockError, ReferencePanic, open_images
+from .table import BlockError, DeviceTable, ReferencePanic, open_images
 
 
 def _dev(device: int) -> torch.device:
@@ -104,6 +106,74 @@ def merge_runs(ctx: Context, ent: DeviceEntries, run_first,
     return merged, src[:n_out], h
 
 
+def entries_from_tables(ctx: Context, tables, check: bool = True,
+                        stream: torch.cuda.Stream | None = None):
+    """tpz_table_runs_layout + tpz_table_runs_entries: resident DeviceTables, in priority order,
+    as (DeviceEntries, run_first): a run per table holding its entries in SsTableIterator order,
+    gathered out of the slotted columns that serve the gets (no upload, no second decode).
+    run_first (numpy, len(tables) + 1) is merge_runs' run table. One read-back (the totals, the
+    first block whose status is neither OK nor OK_SPILLED, and run_first), then the gather.
+    `.bad_block` = (run, block) of that block, or None; with `check` it raises BlockError (with
+    `.table`, `.block`, `.status`), as sub_compact's `?` fails the compaction there."""
+    dev = _dev(ctx.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    tables = list(tables)
+    n_runs = len(tables)
+    if n_runs > _lib.MERGE_MAX_RUNS:
+        raise ValueError(f"{n_runs} tables: tpz_merge_runs takes at most {_lib.MERGE_MAX_RUNS} runs")
+    bf = np.zeros(n_runs + 1, np.uint32)
+    np.cumsum([t.n_blocks for t in tables], out=bf[1:])
+    nb = int(bf[-1])
+    descs = (_lib.Table * max(n_runs, 1))(*[t.table() for t in tables])
+    with torch.cuda.stream(s):      # (the upload and the read-back are torch's: same stream)
+        d_tabs = torch.from_numpy(np.frombuffer(bytes(descs), np.uint8).copy()).to(dev)
+        first = torch.empty(3 * (nb + 1), dtype=torch.int64, device=dev)
+        # d_info (4 u64) and d_run_first (n_runs + 1 u32) in one buffer: one read-back
+        buf = torch.empty(4 + (n_runs + 2) // 2, dtype=torch.int64, device=dev)
+        ctx.table_runs_layout_ptrs(d_tabs.data_ptr(), n_runs, bf.ctypes.data, first.data_ptr(),
+                                   buf.data_ptr() + 32, buf.data_ptr(), s.cuda_stream)
+        h = buf.cpu().numpy()                                           # (waits for the stream)
+        n, kb, vb, bad = (int(x) for x in h[:4].view(np.uint64))
+        run_first = h[4:].view(np.uint32)[:n_runs + 1].astype(np.int64)
+        if n >= 2**32 - 1:
+            raise ValueError(f"{n} entries: a tpz_entries holds fewer than 2^32 - 1")
+        keys = torch.empty(max(kb, 16), dtype=torch.uint8, device=dev)
+        vals = torch.empty(max(vb, 16), dtype=torch.uint8, device=dev)
+        kpos = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        vpos = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        ctx.table_runs_entries_ptrs(d_tabs.data_ptr(), n_runs, bf.ctypes.data, first.data_ptr(),
+                                    keys.data_ptr(), kb, kpos.data_ptr(), vals.data_ptr(), vb,
+                                    vpos.data_ptr(), n, s.cuda_stream)
+    ent = DeviceEntries(keys, kpos, vals, vpos, ctx.device)
+    ent.bad_block = None if bad == 2**64 - 1 else (bad >> 32, bad & 0xFFFFFFFF)
+    if check and ent.bad_block is not None:
+        run, blk = ent.bad_block
+        st = int(tables[run].status[blk].cpu())
+        if st == _lib.BLOCK_CHECKSUM_MISMATCH:    # (the stored CRC is in the block, not the columns)
+            crc = int(tables[run].cols.crc[blk].cpu().numpy().view(np.uint32))
+            text = f"checksum: actual {crc}"
+        else:
+            text = _lib.format_block_error(st) or "entries an iterator cannot read"
+        e = BlockError(f"table {run} block {blk}: {text}")
+        e.table, e.block, e.status = run, blk, st
+        raise e
+    return ent, run_first
+
+
+def _merge_inputs(ctx: Context, regions, stream: torch.cuda.Stream | None) -> DeviceEntries:
+    """compact's and compact_task's inputs, by type: resident DeviceTables go through
+    entries_from_tables (no host concatenation, upload or decode), (bytes, extents) tuples through
+    _merge_regions; then one tpz_merge_runs over a run per table."""
+    regions = list(regions)
+    resident = [isinstance(r, DeviceTable) for r in regions]
+    if regions and all(resident):
+        ent, run_first = entries_from_tables(ctx, regions, stream=stream)
+        return merge_runs(ctx, ent, run_first, stream)[0]
+    if any(resident):
+        raise TypeError("regions mixes DeviceTables with (bytes, extents) tuples")
+    return _merge_regions(ctx, regions, stream)
+
+
 def _merge_regions(ctx: Context, regions, stream: torch.cuda.Stream | None) -> DeviceEntries:
     """The read side and the merge of a compaction: the input tables' blocks through the codec
     step and the flat decode, then one tpz_merge_runs over a run per table."""
@@ -142,12 +212,14 @@ def compact(ctx: Context, regions, block_size: int = 4096, codec: int = 1,
             stream: torch.cuda.Stream | None = None) -> Compacted:
     """One output table of a compaction. `regions`: the input tables' (data-region bytes, block
     extents), in priority order (sub_compact's this_tables + next_tables: an earlier table wins a
-    key). codec: the output's CompressOptions tag (1 Uncompress, 2 Snappy, 3 Lz4)."""
+    key), or the input tables as resident DeviceTables, which are gathered where they lie
+    (entries_from_tables); a mixture of the two is a TypeError. codec: the output's CompressOptions
+    tag (1 Uncompress, 2 Snappy, 3 Lz4)."""
     if codec not in (1, 2, 3):
         raise ValueError(f"codec {codec}")
     dev = _dev(ctx.device)
     s = stream if stream is not None else torch.cuda.current_stream(dev)
-    merged = _merge_regions(ctx, regions, stream)
+    merged = _merge_inputs(ctx, regions, stream)
     first, oext, info = plan_blocks_async(ctx, merged, block_size, s)
     out = encode_blocks_async(ctx, merged, first, oext, info, stream=s)
     _, bad, nb = (int(x) for x in info[:3].cpu().numpy().view(np.uint32))   # (waits for the stream)
@@ -245,7 +317,8 @@ def compact_task(ctx: Context, regions, bounds, block_size: int = 4096, codec: i
     """A whole compaction task (do_compact, src/level.rs:133-222) on the device: the SST files its
     sub-compactions write, as images in one device arena, each ready for one D2H copy.
 
-    `regions`: as for compact(), the input tables in priority order; every table's keys are
+    `regions`: as for compact(), the input tables in priority order, as (bytes, extents) tuples
+    or as resident DeviceTables (then nothing is uploaded or decoded again); every table's keys are
     strictly increasing (with repeated keys the reference's seek lands on any of them).
     `bounds`: the sub-compactions' key ranges, a list of (lower, (upper, inclusive)) as sub_ranges
     returns them; lower is Included. The inputs are merged once and the merged entries split at the
@@ -274,7 +347,7 @@ def _compact_task(ctx: Context, regions, segs, block_size: int, codec: int,
                   false_positive_rate: float, table_capacity: int, s) -> TaskTables:
     dev = _dev(ctx.device)
     stream = s
-    merged = _merge_regions(ctx, regions, stream)
+    merged = _merge_inputs(ctx, regions, stream)
     out = TaskTables()
     out.entries = merged
     out.arena = torch.empty(0, dtype=torch.uint8, device=dev)
@@ -529,9 +602,22 @@ class TableDesc:
 
     @classmethod
     def of(cls, t) -> "TableDesc":
-        """From a table.SsTable (or anything with its fields)."""
+        """From a table.SsTable (or anything with its fields), or from a resident DeviceTable:
+        the block first keys and their positions are read back, the offsets and the meta offset
+        are the stored extents, the biggest key is last_key()."""
         if isinstance(t, cls):
             return t
+        if isinstance(t, DeviceTable):
+            nb = t.n_blocks
+            pos = t.first_pos[:nb + 1].cpu().numpy()
+            if len(pos) != nb + 1:
+                raise ValueError("the DeviceTable was built without its block first keys")
+            fk =t.first_keys[:int(pos[-1])].cpu().numpy().tobytes() if nb else b""
+            keys = [fk[int(pos[i]):int(pos[i + 1])] for i in range(nb)]
+            if not keys:    # init_samllest_biggest_key's block_metas[0]
+                raise ReferencePanic("index out of bounds: the len is 0 but the index is 0")
+            ext = t.ext_host
+            return cls(keys[0], t.last_key(), keys, ext[:nb], int(ext[nb]))
         return cls(t.smallest_key, t.biggest_key, [m.first_key for m in t.block_metas],
                    [m.offset for m in t.block_metas], t.block_meta_offset)
 

@@ -149,6 +149,8 @@ struct tpz_workspace {
   size_t scan_cap = 0;
   void* d_tables = nullptr;     // tpz_sst_finish: key-length partial sums, the CRC's ranges and output
   size_t tables_cap = 0;
+  void* d_runs = nullptr;       // tpz_table_runs_layout: the three scans' partial sums
+  size_t runs_cap = 0;
   uint32_t* h_info = nullptr;   // pinned: tpz_plan_blocks' read-back of its 16-byte info
 };
 
@@ -179,6 +181,7 @@ void free_workspace(tpz_workspace& w) {
   if (w.d_get) (void)hipFree(w.d_get);
   if (w.d_scan) (void)hipFree(w.d_scan);
   if (w.d_tables) (void)hipFree(w.d_tables);
+  if (w.d_runs) (void)hipFree(w.d_runs);
   if (w.h_info) (void)hipHostFree(w.h_info);
   w = tpz_workspace{};
 }
@@ -1790,6 +1793,80 @@ tpz_err tpz_open_metas(tpz_ctx* c, const uint8_t* d_src, uint64_t span_bytes,
   tpz::launch_open_metas(a, (hipStream_t)stream);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
+}
+
+// tpz_table_runs_layout / tpz_table_runs_entries: the run table's rules (n_runs + 1 values, from 0,
+// non-decreasing).
+static bool block_first_ok(const uint32_t* h, uint32_t n_runs) {
+  if (n_runs > TPZ_MERGE_MAX_RUNS || !h || h[0] != 0) return false;
+  for (uint32_t r = 0; r < n_runs; r++)
+    if (h[r] > h[r + 1]) return false;
+  return true;
+}
+
+tpz_err tpz_table_runs_layout(tpz_ctx* c, const tpz_table* d_tables, uint32_t n_runs,
+                              const uint32_t* h_block_first, uint64_t* d_block_first,
+                              uint32_t* d_run_first, uint64_t* d_info, void* stream) {
+  if (!c || !d_block_first || !d_run_first || !d_info || (n_runs && !d_tables))
+    return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_tables | (uintptr_t)d_block_first | (uintptr_t)d_info) & 7u) ||
+      ((uintptr_t)d_run_first & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  if (!block_first_ok(h_block_first, n_runs)) return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  const uint32_t nb = h_block_first[n_runs];
+  void* part = nullptr;
+  if (nb) {
+    std::lock_guard<std::mutex> g(c->mu);
+    tpz_workspace& w = c->ws[stream];
+    tpz_err r = grow(stream, &w.d_runs, &w.runs_cap, 8 * tpz::flat_scan_parts_words(nb));
+    if (r != TPZ_SUCCESS) return r;
+    part = w.d_runs;
+  }
+  tpz::launch_table_runs_layout(d_tables, n_runs, h_block_first, d_block_first, d_run_first, d_info,
+                                static_cast<uint64_t*>(part), (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+static tpz_err table_runs_entries(tpz_ctx* c, const tpz_table* d_tables, uint32_t n_runs,
+                                  const uint32_t* h_block_first, const uint64_t* d_block_first,
+                                  uint8_t* d_keys, uint64_t key_cap, uint64_t* d_kpos,
+                                  uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
+                                  uint64_t entry_cap, bool aligned, void* stream) {
+  if (!c || !d_block_first || !d_kpos || !d_vpos || (n_runs && !d_tables) ||
+      (key_cap && !d_keys) || (val_cap && !d_vals))
+    return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
+      (((uintptr_t)d_tables | (uintptr_t)d_block_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u))
+    return TPZ_ERR_INVALID_ARG;
+  if (!block_first_ok(h_block_first, n_runs)) return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::launch_table_runs_entries(d_tables, n_runs, h_block_first, d_block_first, d_keys, key_cap,
+                                 d_kpos, d_vals, val_cap, d_vpos, entry_cap, aligned,
+                                 (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_table_runs_entries(tpz_ctx* c, const tpz_table* d_tables, uint32_t n_runs,
+                               const uint32_t* h_block_first, const uint64_t* d_block_first,
+                               uint8_t* d_keys, uint64_t key_cap, uint64_t* d_kpos, uint8_t* d_vals,
+                               uint64_t val_cap, uint64_t* d_vpos, uint64_t entry_cap, void* stream) {
+  return table_runs_entries(c, d_tables, n_runs, h_block_first, d_block_first, d_keys, key_cap,
+                            d_kpos, d_vals, val_cap, d_vpos, entry_cap, false, stream);
+}
+
+// Diagnostic export (not in tpz_gpu.h; tools/runs_probe.py): the gather with its form chosen,
+// aligned != 0: aligned 16-byte loads and a funnel shift in place of copydev::wave_copy's
+// unaligned loads (it measured slower, DESIGN.md §3.18: the product call takes wave_copy).
+extern "C" tpz_err tpz_debug_table_runs_entries(
+    tpz_ctx* c, const tpz_table* d_tables, uint32_t n_runs, const uint32_t* h_block_first,
+    const uint64_t* d_block_first, uint8_t* d_keys, uint64_t key_cap, uint64_t* d_kpos,
+    uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos, uint64_t entry_cap, uint32_t aligned,
+    void* stream) {
+  return table_runs_entries(c, d_tables, n_runs, h_block_first, d_block_first, d_keys, key_cap,
+                            d_kpos, d_vals, val_cap, d_vpos, entry_cap, aligned != 0, stream);
 }
 
 uint64_t tpz_host_xxh3_64(const uint8_t* h_buf, uint64_t len) {

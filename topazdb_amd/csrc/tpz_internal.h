@@ -575,6 +575,18 @@ struct OpenIndexLaunch {
 void launch_open_index(const OpenIndexLaunch& a, hipStream_t stream);
 void launch_open_metas(const OpenIndexLaunch& a, hipStream_t stream);
 
+// tpz_table_runs_layout / tpz_table_runs_entries (tpz_runs.hip): resident tables as merge runs.
+// h_block_first: host, n_runs + 1, checked by the caller; first: 3 x (B + 1) u64; part =
+// flat_scan_parts_words(B) u64 of device scratch. aligned: the aligned-load form of the gather
+// (the diagnostic export's; false: copydev::wave_copy, the product's).
+void launch_table_runs_layout(const tpz_table* tabs, uint32_t n_runs, const uint32_t* h_block_first,
+                              uint64_t* first, uint32_t* run_first, uint64_t* info, uint64_t* part,
+                              hipStream_t stream);
+void launch_table_runs_entries(const tpz_table* tabs, uint32_t n_runs, const uint32_t* h_block_first,
+                               const uint64_t* first, uint8_t* keys, uint64_t key_cap, uint64_t* kpos,
+                               uint8_t* vals, uint64_t val_cap, uint64_t* vpos, uint64_t entry_cap,
+                               bool aligned, hipStream_t stream);
+
 // tpz_compress_blocks (tpz_compress.hip): scratch bytes for the per-block slots; the snappy
 // encode, the scan of the sizes into dst_ext and the packing into dst.
 uint64_t compress_scratch_bytes(uint64_t src_bytes, uint32_t n_blocks);

@@ -205,6 +205,7 @@ class DeviceTable:
     def _decode(self, batch: DeviceBatch, has_codec: bool, exact_ends: bool) -> None:
         """The codec step where some block needs it, then one tpz_decode_blocks launch."""
         nb = self.n_blocks = batch.n_blocks
+        self.ext_host = batch.ext_host      # the stored extents: BlockMeta::offset + the meta offset
         self.codec = None
         if has_codec:
             batch, st = decompress_batch(self.ctx, batch)
