@@ -21,15 +21,18 @@ VARS = {"TPZ_BLOOM_ATOMIC": "tpz_api.cpp", "TPZ_BLOOM_GATHER": "tpz_seek.hip",
 
 
 def bloom_cases(ctx) -> int:
-    """The bloom parity cases a child runs: 6 slices, 275 slices (tests/test_gpu_bloom_slices.py)
-    and the largest filter of tests/test_gpu_encode.py's test. Returns how many ran."""
+    """The bloom parity cases a child runs: 6 slices, 275 slices (tests/test_gpu_bloom_slices.py),
+    the largest filter of tests/test_gpu_encode.py's test and the keys of every length up to
+    65,535 bytes (tests/test_gpu_xxh3_lengths.py). Returns how many ran."""
     from test_gpu_bloom_slices import TINY, build_and_compare, reach
     from test_gpu_encode import test_device_bloom_build
+    from test_gpu_xxh3_lengths import long_key_bloom_case
     assert reach(2000, TINY)[:2] == (6, 3) and reach(100_000, TINY)[:2] == (275, 123)
     build_and_compare(ctx, 2000, TINY)
     build_and_compare(ctx, 100_000, TINY)
     test_device_bloom_build(ctx, 60000, 0.001, 24)
-    return 3
+    long_key_bloom_case(ctx)
+    return 4
 
 
 def plan_cases(ctx) -> int:
@@ -78,4 +81,4 @@ def test_env_selected_path(var, cases):
                        text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("ENV-PATH")]
-    assert lines == [f"ENV-PATH {var} cases 3 OK"]
+    assert lines == [f"ENV-PATH {var} cases {4 if cases == 'bloom_cases' else 3} OK"]
