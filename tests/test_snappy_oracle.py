@@ -3,7 +3,12 @@ trusted as the checker: the known answers of tests/golden/snappy_kat.json (hand-
 every element kind and the streams snap's decoder rejects, from the published format), the C
 oracle against the independent Python restatement on random and mutated streams, and round
 trips of both compressors. No snappy library exists in this image: parity of snap's exact
-error *kinds* is unpinned; that a stream is rejected is pinned."""
+error *kinds* is unpinned; that a stream is rejected is pinned.
+
+The streams here come from the two compressors and from mutations of their output, so they hold
+no literal after a literal, no wide literal header and no copy shorter than 4 bytes. The pin for
+element mixes is the generator of tests/_snappy_cases.py, which writes a stream and its bytes
+without a decoder: tests/test_snappy_cases.py checks both restatements against it."""
 import json
 import os
 import importlib.util
