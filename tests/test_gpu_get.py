@@ -480,3 +480,28 @@ def test_no_tables_and_no_levels(ctx):
         got = DeviceLevels(ctx, levels).get_batch(qs)
         assert_equal(got, [M.Get(M.ABSENT, 0, M.NONE, M.NONE, M.NONE, b"")] * 3, qs)
         assert DeviceLevels(ctx, levels).get(b"a") is None
+
+
+def test_no_keys(ctx):
+    """n_keys == 0 over one small table: tpz_get_keys zeroes the 8 bytes at d_val_pos and writes
+    nothing else; tpz_get_values succeeds without touching d_vals (also with val_cap == 0 and
+    keys to gather)."""
+    ents = [(b"a", b"1"), (b"b", b"22"), (b"c", b"")]
+    dl = device_levels(ctx, [[M.build_pieces(ents, 64)]])
+    assert_equal(dl.get_batch([]), [], [])
+    dev, stream = dl.dev, torch.cuda.current_stream(dl.dev).cuda_stream
+    cols = {k: torch.full((2,), 0x5A, dtype=t, device=dev) for k, t in
+            (("result", torch.uint8), ("status", torch.uint8), ("table", torch.int32),
+             ("block", torch.int32), ("entry", torch.int32), ("val_pos", torch.int64))}
+    qp = torch.zeros(1, dtype=torch.int64, device=dev)
+    ctx.get_keys_ptrs(dl.d_tables.data_ptr(), dl.n_tables, dl.level_first.ctypes.data, dl.n_levels,
+                      0, qp.data_ptr(), 0, *(cols[k].data_ptr() for k in cols), stream)
+    vals = torch.full((16,), 0x5A, dtype=torch.uint8, device=dev)
+    args = [cols[k].data_ptr() for k in ("result", "table", "block", "entry", "val_pos")]
+    ctx.get_values_ptrs(dl.d_tables.data_ptr(), dl.n_tables, 0, *args, vals.data_ptr(), 16, stream)
+    ctx.get_values_ptrs(dl.d_tables.data_ptr(), dl.n_tables, 2, *args, vals.data_ptr(), 0, stream)
+    torch.cuda.synchronize()
+    assert cols["val_pos"].tolist() == [0, 0x5A]
+    for k in ("result", "status", "table", "block", "entry"):
+        assert cols[k].tolist() == [0x5A, 0x5A], k
+    assert vals.tolist() == [0x5A] * 16

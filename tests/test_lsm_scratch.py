@@ -1,5 +1,5 @@
-"""The kernels over memtable runs (tpz_mem.hip) use no scratch (private segment) memory: the run
-descriptors are read from HBM field by field, as the walk reads the tables', and the gather moves
+"""The kernels over memtable runs (tpz_mem.hip, tpz_get.hip, tpz_scan.hip) use no scratch
+(private segment) memory: the run descriptors are read from HBM field by field, as the walk reads the tables', and the gather moves
 bytes straight between the columns. Read from the built library as tests/test_scratch.py does; no
 GPU needed."""
 import os

@@ -118,8 +118,29 @@ std::vector<uint32_t> build_rep_tables(const std::vector<uint32_t>& range) {
 
 }  // namespace
 
+// The grow-only scratch buffers of a workspace, one per kind of call (ws_buffer below).
+enum ws_id {
+  kWsAcc,      // tpz_crc32_ranges: one u32 accumulator per range (the layout calls' partial sums too)
+  kWsPlan0,    // tpz_plan_blocks: nx + per-workgroup maxima + info
+  kWsPlan1,    // tpz_plan_blocks: the transfer tables + chunk counts
+  kWsBloom,    // tpz_bloom_build: probe buckets + slice histograms
+  kWsComp,     // tpz_compress_blocks: the per-block scratch slots + scan parts
+  kWsMerge,    // tpz_merge_runs: prefixes, id lists, tile partitions, scan arrays (tpz_mem_build
+               // and tpz_wal_entries use it too, in stream order)
+  kWsGet,      // tpz_get_keys: the value-length scan's partial sums
+  kWsScan,     // tpz_scan_ranges: cursors, their statuses, scan partial sums; tpz_scan_entries:
+               // the scans' byte bases and partial sums (every flavour)
+  kWsTables,   // tpz_sst_finish: key-length partial sums, the CRC's ranges and output
+  kWsRuns,     // tpz_table_runs_layout: the three scans' partial sums
+  kWsBufs
+};
+struct ws_buf {
+  void* d = nullptr;
+  size_t cap = 0;   // bytes
+};
+
 // Device workspace of one stream: the big-path and spill-path worklists, the big path's
-// per-workgroup entry tables and the range-CRC accumulators. Decodes on different streams run
+// per-workgroup entry tables and the scratch buffers above. Decodes on different streams run
 // concurrently, so each stream has its own; calls on one stream are ordered by the stream.
 struct tpz_workspace {
   uint32_t* d_defer = nullptr;  // [0] big/codec counter, [1] spill counter, [2] bigwave counter,
@@ -129,28 +150,7 @@ struct tpz_workspace {
   uint32_t* d_tail = nullptr;   // the decode's tpz::kTailCounters (zero between decodes) + the
                                 // sticky tpz::kTailError word
   uint64_t* d_big_scratch = nullptr;
-  uint32_t* d_acc = nullptr;    // acc_cap per-range accumulators of tpz_crc32_ranges
-  uint32_t acc_cap = 0;
-  void* d_plan0 = nullptr;      // tpz_plan_blocks: nx + per-workgroup maxima + info
-  size_t plan0_cap = 0;
-  void* d_plan1 = nullptr;      // tpz_plan_blocks: the transfer tables + chunk counts
-  size_t plan1_cap = 0;
-  void* d_bloom = nullptr;      // tpz_bloom_build: probe buckets + slice histograms
-  size_t bloom_cap = 0;
-  void* d_comp = nullptr;       // tpz_compress_blocks: the per-block scratch slots + scan parts
-  size_t comp_cap = 0;
-  void* d_merge = nullptr;      // tpz_merge_runs: prefixes, id lists, tile partitions, scan arrays
-                                // (tpz_mem_build and tpz_wal_entries use it too, in stream order)
-  size_t merge_cap = 0;
-  void* d_get = nullptr;        // tpz_get_keys: the value-length scan's partial sums
-  size_t get_cap = 0;
-  void* d_scan = nullptr;       // tpz_scan_ranges: cursors, their statuses, scan partial sums;
-                                // tpz_scan_entries: the scans' byte bases and partial sums
-  size_t scan_cap = 0;
-  void* d_tables = nullptr;     // tpz_sst_finish: key-length partial sums, the CRC's ranges and output
-  size_t tables_cap = 0;
-  void* d_runs = nullptr;       // tpz_table_runs_layout: the three scans' partial sums
-  size_t runs_cap = 0;
+  ws_buf buf[kWsBufs];
   uint32_t* h_info = nullptr;   // pinned: tpz_plan_blocks' read-back of its 16-byte info
 };
 
@@ -172,54 +172,41 @@ void free_workspace(tpz_workspace& w) {
   if (w.d_defer) (void)hipFree(w.d_defer);
   if (w.d_tail) (void)hipFree(w.d_tail);
   if (w.d_big_scratch) (void)hipFree(w.d_big_scratch);
-  if (w.d_acc) (void)hipFree(w.d_acc);
-  if (w.d_plan0) (void)hipFree(w.d_plan0);
-  if (w.d_plan1) (void)hipFree(w.d_plan1);
-  if (w.d_bloom) (void)hipFree(w.d_bloom);
-  if (w.d_comp) (void)hipFree(w.d_comp);
-  if (w.d_merge) (void)hipFree(w.d_merge);
-  if (w.d_get) (void)hipFree(w.d_get);
-  if (w.d_scan) (void)hipFree(w.d_scan);
-  if (w.d_tables) (void)hipFree(w.d_tables);
-  if (w.d_runs) (void)hipFree(w.d_runs);
+  for (ws_buf& b : w.buf)
+    if (b.d) (void)hipFree(b.d);
   if (w.h_info) (void)hipHostFree(w.h_info);
   w = tpz_workspace{};
 }
 
-// The stream's range-CRC accumulators, grown to n ranges. Caller holds c->mu.
-tpz_err get_acc(tpz_ctx* c, void* stream, uint32_t n, uint32_t** out) {
-  tpz_workspace& w = c->ws[stream];
-  if (!w.d_acc || w.acc_cap < n) {
-    uint32_t* d = nullptr;
-    TPZ_HIP(hipMalloc(&d, (size_t)n * 4));
-    if (w.d_acc) {
+// Buffer `which` of the stream's workspace, grown to `bytes` (grow-only; the stream is idle or
+// only uses it in order: a buffer is replaced after the stream's pending work is done). Caller
+// holds c->mu: for the sites that take two buffers under one lock.
+template <class T>
+tpz_err grow(tpz_ctx* c, void* stream, ws_id which, size_t bytes, T** out) {
+  ws_buf& b = c->ws[stream].buf[which];
+  if (!b.d || b.cap < bytes) {
+    void* d = nullptr;
+    TPZ_HIP(hipMalloc(&d, bytes));
+    if (b.d) {
       (void)hipStreamSynchronize((hipStream_t)stream);
-      (void)hipFree(w.d_acc);
+      (void)hipFree(b.d);
     }
-    w.d_acc = d;
-    w.acc_cap = n;
+    b.d = d;
+    b.cap = bytes;
   }
-  *out = w.d_acc;
+  *out = static_cast<T*>(b.d);
   return TPZ_SUCCESS;
 }
-
-// A grow-only device buffer of the stream's workspace (the stream is idle or only uses it in
-// order: a buffer is replaced after the stream's pending work is done). Caller holds c->mu.
-tpz_err grow(void* stream, void** buf, size_t* cap, size_t bytes) {
-  if (*buf && *cap >= bytes) return TPZ_SUCCESS;
-  void* d = nullptr;
-  TPZ_HIP(hipMalloc(&d, bytes));
-  if (*buf) {
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(*buf);
-  }
-  *buf = d;
-  *cap = bytes;
-  return TPZ_SUCCESS;
+// The same, taking the lock: every call that needs one buffer.
+template <class T>
+tpz_err ws_buffer(tpz_ctx* c, void* stream, ws_id which, size_t bytes, T** out) {
+  std::lock_guard<std::mutex> g(c->mu);
+  return grow(c, stream, which, bytes, out);
 }
 
-// The stream's workspace, grown to max_blocks. Caller holds c->mu.
+// The stream's workspace, its worklists grown to max_blocks.
 tpz_err get_workspace(tpz_ctx* c, void* stream, uint32_t max_blocks, tpz_workspace** out) {
+  std::lock_guard<std::mutex> g(c->mu);
   tpz_workspace& w = c->ws[stream];
   if (!w.d_big_scratch)
     TPZ_HIP(hipMalloc(&w.d_big_scratch, (size_t)c->num_cus * 2 * tpz::kBigMaxSlots * sizeof(uint64_t)));
@@ -239,6 +226,25 @@ tpz_err get_workspace(tpz_ctx* c, void* stream, uint32_t max_blocks, tpz_workspa
     w.defer_cap = max_blocks;
   }
   *out = &w;
+  return TPZ_SUCCESS;
+}
+
+// tpz_decode_check / tpz_decompress_check: one sticky word of the stream's tail, read and cleared
+// in stream order (after every call queued before it; the null stream is not involved), then
+// waited for. `what` names the caller for a stream that has no workspace yet.
+tpz_err take_tail_word(tpz_ctx* c, void* stream, int word, const char* what, uint32_t* flag) {
+  TPZ_HIP(hipSetDevice(c->device));
+  uint32_t* tail = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->ws.find(stream);
+    if (it != c->ws.end()) tail = it->second.d_tail;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (!tail) return hip_fail(hipStreamSynchronize(s), what);
+  TPZ_HIP(hipMemcpyAsync(flag, tail + word, 4, hipMemcpyDeviceToHost, s));
+  TPZ_HIP(hipMemsetAsync(tail + word, 0, 4, s));
+  TPZ_HIP(hipStreamSynchronize(s));
   return TPZ_SUCCESS;
 }
 
@@ -328,7 +334,6 @@ void tpz_ctx_destroy(tpz_ctx* c) {
 tpz_err tpz_ctx_reserve(tpz_ctx* c, uint32_t max_blocks, void* stream) {
   if (!c) return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
-  std::lock_guard<std::mutex> g(c->mu);
   tpz_workspace* w = nullptr;
   return get_workspace(c, stream, max_blocks, &w);
 }
@@ -348,11 +353,8 @@ tpz_err tpz_decode_blocks(tpz_ctx* c, const tpz_batch* b, const tpz_columns* o, 
     return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
   tpz_workspace* w = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err r = get_workspace(c, stream, b->n_blocks, &w);
-    if (r != TPZ_SUCCESS) return r;
-  }
+  tpz_err r = get_workspace(c, stream, b->n_blocks, &w);
+  if (r != TPZ_SUCCESS) return r;
   uint32_t* tail = w->d_tail;
   hipStream_t s = (hipStream_t)stream;
   tpz::LaunchArgs a{};
@@ -389,22 +391,9 @@ tpz_err tpz_decode_blocks(tpz_ctx* c, const tpz_batch* b, const tpz_columns* o, 
 
 tpz_err tpz_decode_check(tpz_ctx* c, void* stream) {
   if (!c) return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  uint32_t* tail = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->ws.find(stream);
-    if (it != c->ws.end()) tail = it->second.d_tail;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (!tail) return hip_fail(hipStreamSynchronize(s), "tpz_decode_check");
-  // read and clear the stream's flag in stream order (after every decode queued before it; the
-  // null stream is not involved), then wait for both
   uint32_t flag = 0;
-  TPZ_HIP(hipMemcpyAsync(&flag, tail + tpz::kTailError, 4, hipMemcpyDeviceToHost, s));
-  TPZ_HIP(hipMemsetAsync(tail + tpz::kTailError, 0, 4, s));
-  TPZ_HIP(hipStreamSynchronize(s));
-  if (!flag) return TPZ_SUCCESS;
+  tpz_err r = take_tail_word(c, stream, tpz::kTailError, "tpz_decode_check", &flag);
+  if (r != TPZ_SUCCESS || !flag) return r;
   // bit 0: a tail workgroup's bounded wait; bit 1: a wave path row wait; bit 2: a wave path row
   // slot overwritten before its reader got to it (tpz_decode.hip claim_chunk)
   g_last_error = (flag & 1u) ? "tpz_decode_blocks: a tail workgroup's wait for the big path timed out; "
@@ -421,11 +410,8 @@ static tpz_err crc_ranges(tpz_ctx* c, const tpz_batch* r, uint32_t trailer, uint
   if (!r->d_src || !r->d_ext) return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
   uint32_t* acc = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err e = get_acc(c, stream, r->n_blocks, &acc);
-    if (e != TPZ_SUCCESS) return e;
-  }
+  tpz_err e = ws_buffer(c, stream, kWsAcc, (size_t)r->n_blocks * 4, &acc);
+  if (e != TPZ_SUCCESS) return e;
   hipStream_t s = (hipStream_t)stream;
   TPZ_HIP(hipMemsetAsync(acc, 0, (size_t)r->n_blocks * 4, s));
   tpz::CrcLaunch a{};
@@ -475,21 +461,9 @@ tpz_err tpz_decompressed_sizes_claimed(tpz_ctx* c, const tpz_batch* b, uint64_t*
 
 tpz_err tpz_decompress_check(tpz_ctx* c, void* stream) {
   if (!c) return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  uint32_t* tail = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->ws.find(stream);
-    if (it != c->ws.end()) tail = it->second.d_tail;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (!tail) return hip_fail(hipStreamSynchronize(s), "tpz_decompress_check");
-  // read and clear the stream's word in stream order, as tpz_decode_check does
   uint32_t flag = 0;
-  TPZ_HIP(hipMemcpyAsync(&flag, tail + tpz::kTailCodecInexact, 4, hipMemcpyDeviceToHost, s));
-  TPZ_HIP(hipMemsetAsync(tail + tpz::kTailCodecInexact, 0, 4, s));
-  TPZ_HIP(hipStreamSynchronize(s));
-  if (!flag) return TPZ_SUCCESS;
+  tpz_err r = take_tail_word(c, stream, tpz::kTailCodecInexact, "tpz_decompress_check", &flag);
+  if (r != TPZ_SUCCESS || !flag) return r;
   g_last_error = "tpz_decompress_blocks: an LZ4 block's claimed size was not its decoded length "
                  "(an Err or a short stream); size the batch with tpz_decompressed_sizes and "
                  "decompress it again";
@@ -504,11 +478,8 @@ tpz_err tpz_decompress_blocks(tpz_ctx* c, const tpz_batch* b, uint8_t* d_dst,
     return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
   tpz_workspace* w = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err r = get_workspace(c, stream, b->n_blocks, &w);
-    if (r != TPZ_SUCCESS) return r;
-  }
+  tpz_err r = get_workspace(c, stream, b->n_blocks, &w);
+  if (r != TPZ_SUCCESS) return r;
   hipStream_t s = (hipStream_t)stream;
   tpz::CodecLaunch a{};
   a.src = b->d_src;
@@ -531,14 +502,12 @@ tpz_err tpz_entry_first(tpz_ctx* c, const tpz_batch* b, uint64_t* d_first, void*
   if (!c || !b || !d_first) return TPZ_ERR_INVALID_ARG;
   if (b->n_blocks && (!b->d_src || !b->d_ext)) return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
-  uint32_t* part = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err e = get_acc(c, stream, 2 * (uint32_t)tpz::entry_first_parts(b->n_blocks), &part);
-    if (e != TPZ_SUCCESS) return e;
-  }
-  tpz::launch_entry_first(b->d_src, b->d_ext, b->src_bytes, b->n_blocks, d_first,
-                          reinterpret_cast<uint64_t*>(part), (hipStream_t)stream);
+  uint64_t* part = nullptr;
+  tpz_err e = ws_buffer(c, stream, kWsAcc, 8 * (size_t)(uint32_t)tpz::entry_first_parts(b->n_blocks),
+                        &part);
+  if (e != TPZ_SUCCESS) return e;
+  tpz::launch_entry_first(b->d_src, b->d_ext, b->src_bytes, b->n_blocks, d_first, part,
+                          (hipStream_t)stream);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }
@@ -547,14 +516,12 @@ tpz_err tpz_flat_layout(tpz_ctx* c, const tpz_batch* b, uint64_t* d_first, void*
   if (!c || !b || !d_first) return TPZ_ERR_INVALID_ARG;
   if (b->n_blocks && (!b->d_src || !b->d_ext)) return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
-  uint32_t* part = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err e = get_acc(c, stream, 2 * (uint32_t)tpz::flat_scan_parts_words(b->n_blocks), &part);
-    if (e != TPZ_SUCCESS) return e;
-  }
-  tpz::launch_flat_layout(b->d_src, b->d_ext, b->src_bytes, b->n_blocks, d_first,
-                          reinterpret_cast<uint64_t*>(part), c->num_cus, (hipStream_t)stream);
+  uint64_t* part = nullptr;
+  tpz_err e = ws_buffer(c, stream, kWsAcc,
+                        8 * (size_t)(uint32_t)tpz::flat_scan_parts_words(b->n_blocks), &part);
+  if (e != TPZ_SUCCESS) return e;
+  tpz::launch_flat_layout(b->d_src, b->d_ext, b->src_bytes, b->n_blocks, d_first, part, c->num_cus,
+                          (hipStream_t)stream);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }
@@ -576,11 +543,8 @@ tpz_err tpz_decode_blocks_flat(tpz_ctx* c, const tpz_batch* b, const tpz_flat_co
     return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
   tpz_workspace* w = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err r = get_workspace(c, stream, b->n_blocks, &w);
-    if (r != TPZ_SUCCESS) return r;
-  }
+  tpz_err r = get_workspace(c, stream, b->n_blocks, &w);
+  if (r != TPZ_SUCCESS) return r;
   uint32_t* tail = w->d_tail;
   const uint64_t st = (uint64_t)b->n_blocks + 1;
   tpz::LaunchArgs a{};
@@ -633,14 +597,9 @@ tpz_err tpz_compress_blocks(tpz_ctx* c, const tpz_batch* b, uint32_t codec, uint
   TPZ_HIP(hipSetDevice(c->device));
   const uint64_t scratch = tpz::compress_scratch_bytes(b->src_bytes, b->n_blocks);
   const uint64_t parts = (uint64_t)tpz::flat_scan_parts_words(b->n_blocks);
-  tpz_workspace* w = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    w = &c->ws[stream];
-    tpz_err r = grow(stream, &w->d_comp, &w->comp_cap, ((scratch + 15) & ~15ull) + 8 * parts);
-    if (r != TPZ_SUCCESS) return r;
-  }
-  uint8_t* sc = static_cast<uint8_t*>(w->d_comp);
+  uint8_t* sc = nullptr;
+  tpz_err r = ws_buffer(c, stream, kWsComp, ((scratch + 15) & ~15ull) + 8 * parts, &sc);
+  if (r != TPZ_SUCCESS) return r;
   tpz::launch_compress(b->d_src, b->d_ext, b->src_bytes, b->n_blocks, codec, sc, d_dst_ext,
                        reinterpret_cast<uint64_t*>(sc + ((scratch + 15) & ~15ull)), d_dst,
                        c->num_cus, (hipStream_t)stream);
@@ -679,11 +638,8 @@ tpz_err tpz_verify_files_flat_layout(tpz_ctx* c, const tpz_batch* blocks,
   const uint64_t words = 2 * parts + blocks->n_blocks + tails->n_blocks;
   if (words > 0xFFFFFFFFull) return TPZ_ERR_INVALID_ARG;
   uint32_t* ws = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err e = get_acc(c, stream, (uint32_t)words, &ws);
-    if (e != TPZ_SUCCESS) return e;
-  }
+  tpz_err e = ws_buffer(c, stream, kWsAcc, (size_t)words * 4, &ws);
+  if (e != TPZ_SUCCESS) return e;
   tpz::OpenLaunch a{};
   a.src = blocks->d_src;
   a.bext = blocks->d_ext;
@@ -764,11 +720,8 @@ tpz_err tpz_bloom_build(tpz_ctx* c, const uint8_t* d_keys, const uint64_t* d_key
   const uint64_t work = atomic_only ? 0 : tpz::bloom_build_work_bytes(n_keys, k, (len - 1) * 8);
   void* d_work = nullptr;
   if (work && n_keys) {   // the stream's grow-only scratch (stream-ordered reuse)
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r2 = grow(stream, &w.d_bloom, &w.bloom_cap, work);
-    if (r2 != TPZ_SUCCESS) return r2;
-    d_work = w.d_bloom;
+    r = ws_buffer(c, stream, kWsBloom, work, &d_work);
+    if (r != TPZ_SUCCESS) return r;
   }
   tpz::BloomBuildLaunch a{d_keys, d_key_pos, n_keys, k, (len - 1) * 8, d_filter, (len + 3) / 4,
                           d_work};
@@ -802,17 +755,11 @@ static tpz_err plan_launch(tpz_ctx* c, const tpz_entries* en, uint32_t block_siz
                            uint64_t* d_ext, uint32_t* info, void* stream, uint64_t* h_bad) {
   hipStream_t s = (hipStream_t)stream;
   const uint32_t n = en->n_entries;
-  std::unique_lock<std::mutex> lk(c->mu);
-  tpz_workspace& w = c->ws[stream];
-  lk.unlock();
   const size_t nwg = ((size_t)n + tpz::kPlanNextPer - 1) / tpz::kPlanNextPer;              // plan_next_kernel workgroups
   const size_t nx_words = (size_t)n + 2 * nwg + 2;           // nx, per-workgroup maxima and bad
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err r = grow(stream, &w.d_plan0, &w.plan0_cap, (nx_words + 4) * 4);
-    if (r != TPZ_SUCCESS) return r;
-  }
-  uint32_t* nx = static_cast<uint32_t*>(w.d_plan0);
+  uint32_t* nx = nullptr;
+  tpz_err r = ws_buffer(c, stream, kWsPlan0, (nx_words + 4) * 4, &nx);
+  if (r != TPZ_SUCCESS) return r;
   tpz::PlanLaunch a{};
   a.phase = 0;
   a.kpos = en->d_kpos;
@@ -841,12 +788,8 @@ static tpz_err plan_launch(tpz_ctx* c, const tpz_entries* en, uint32_t block_siz
     a.chunk = a.w > tpz::kPlanChunk ? a.w : tpz::kPlanChunk;
   }
   const uint64_t K = (n + (uint64_t)a.chunk - 1) / a.chunk;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err r = grow(stream, &w.d_plan1, &w.plan1_cap, (2 * K * a.w + K + 4) * 4);
-    if (r != TPZ_SUCCESS) return r;
-  }
-  a.tab_a = static_cast<int*>(w.d_plan1);
+  r = ws_buffer(c, stream, kWsPlan1, (2 * K * a.w + K + 4) * 4, &a.tab_a);
+  if (r != TPZ_SUCCESS) return r;
   a.tab_b = a.tab_a + K * a.w;
   a.cnt = reinterpret_cast<uint32_t*>(a.tab_b + K * a.w);
   a.n_blocks = info + 2;
@@ -883,9 +826,8 @@ tpz_err tpz_plan_blocks(tpz_ctx* c, const tpz_entries* en, uint32_t block_size, 
     std::lock_guard<std::mutex> g(c->mu);
     tpz_workspace& w = c->ws[stream];
     const size_t nwg = ((size_t)en->n_entries + tpz::kPlanNextPer - 1) / tpz::kPlanNextPer;
-    r = grow(stream, &w.d_plan0, &w.plan0_cap, ((size_t)en->n_entries + 2 * nwg + 2 + 4) * 4);
-    if (r == TPZ_SUCCESS)
-      info = static_cast<uint32_t*>(w.d_plan0) + (size_t)en->n_entries + 2 * nwg + 2;
+    r = grow(c, stream, kWsPlan0, ((size_t)en->n_entries + 2 * nwg + 2 + 4) * 4, &info);
+    if (r == TPZ_SUCCESS) info += (size_t)en->n_entries + 2 * nwg + 2;
     if (r == TPZ_SUCCESS && !w.h_info && hipHostMalloc(&w.h_info, 16) != hipSuccess) {
       w.h_info = nullptr;
       r = TPZ_ERR_NOMEM;
@@ -938,11 +880,8 @@ static tpz_err encode_launch(tpz_ctx* c, const tpz_entries* en, const uint32_t* 
   TPZ_HIP(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   tpz_workspace* w = nullptr;    // the big-block worklist: the stream's decode worklist
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_err r = get_workspace(c, stream, n_blocks, &w);
-    if (r != TPZ_SUCCESS) return r;
-  }
+  tpz_err r = get_workspace(c, stream, n_blocks, &w);
+  if (r != TPZ_SUCCESS) return r;
   tpz::EncodeLaunch a{};
   a.keys = en->d_keys;
   a.kpos = en->d_kpos;
@@ -1008,13 +947,8 @@ tpz_err tpz_merge_runs(tpz_ctx* c, const tpz_entries* en, const uint32_t* h_run_
       (!d_out_keys && en->key_bytes) || (!d_out_vals && en->val_bytes))
     return TPZ_ERR_INVALID_ARG;
   void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_merge, &w.merge_cap, tpz::merge_work_bytes(n, n_runs));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_merge;
-  }
+  tpz_err e = ws_buffer(c, stream, kWsMerge, tpz::merge_work_bytes(n, n_runs), &work);
+  if (e != TPZ_SUCCESS) return e;
   tpz::MergeLaunch a{};
   a.keys = en->d_keys;
   a.kpos = en->d_kpos;
@@ -1065,13 +999,8 @@ static tpz_err mem_build(tpz_ctx* c, const tpz_entries* en, uint32_t mode, const
     return TPZ_SUCCESS;
   }
   void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_merge, &w.merge_cap, tpz::membuild_work_bytes(n));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_merge;
-  }
+  tpz_err r = ws_buffer(c, stream, kWsMerge, tpz::membuild_work_bytes(n), &work);
+  if (r != TPZ_SUCCESS) return r;
   tpz::MemBuildLaunch a{en->d_keys, en->d_kpos, en->key_bytes, en->d_vals, en->d_vpos,
                         en->val_bytes, n, mode, d_version, d_out_keys, d_out_kpos, d_out_vals,
                         d_out_vpos, d_out_prefix, d_src_entry, d_out_version, d_info, work,
@@ -1120,13 +1049,8 @@ tpz_err tpz_wal_entries(tpz_ctx* c, const uint8_t* d_image, uint64_t image_bytes
     return TPZ_SUCCESS;
   }
   void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_merge, &w.merge_cap, tpz::wal_entries_work_bytes(n_records));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_merge;
-  }
+  tpz_err r = ws_buffer(c, stream, kWsMerge, tpz::wal_entries_work_bytes(n_records), &work);
+  if (r != TPZ_SUCCESS) return r;
   tpz::WalEntriesLaunch a{d_image, image_bytes, d_rec, n_records, d_keys, d_kpos, d_vals, d_vpos,
                           d_info, work};
   TPZ_HIP(tpz::launch_wal_entries(a, s));
@@ -1144,13 +1068,24 @@ static bool level_first_ok(const uint32_t* h, uint32_t n_levels, uint32_t n_tabl
   return true;
 }
 
-tpz_err tpz_get_keys(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
-                     const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
-                     const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
-                     uint8_t* d_status, uint32_t* d_table, uint32_t* d_block, uint32_t* d_entry,
-                     uint64_t* d_val_pos, void* stream) {
+using tpz::Flavour;
+
+// tpz_lsm_* / tpz_level_scan_*: d_runs holds n_runs <= TPZ_MEM_MAX_RUNS descriptors (the tables'
+// calls pass none).
+static bool runs_ok(const tpz_mem_run* d_runs, uint32_t n_runs) {
+  return n_runs <= TPZ_MEM_MAX_RUNS && (n_runs == 0 || d_runs) && !((uintptr_t)d_runs & 7u);
+}
+
+// The query calls: one implementation per operation, the exported calls below forward to it with
+// their flavour (tables: no runs). Every argument check precedes hipSetDevice.
+static tpz_err get_keys(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                        const tpz_get_table* d_tables, uint32_t n_tables,
+                        const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                        const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                        uint8_t* d_status, uint32_t* d_table, uint32_t* d_block, uint32_t* d_entry,
+                        uint64_t* d_val_pos, void* stream) {
   if (!c || !d_key_pos || !d_result || !d_status || !d_table || !d_block || !d_entry || !d_val_pos ||
-      (n_tables && !d_tables))
+      (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
     return TPZ_ERR_INVALID_ARG;
   if (!level_first_ok(h_level_first, n_levels, n_tables) || n_keys == 0xFFFFFFFFu)
     return TPZ_ERR_INVALID_ARG;
@@ -1163,27 +1098,23 @@ tpz_err tpz_get_keys(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_table
     TPZ_HIP(hipMemsetAsync(d_val_pos, 0, 8, s));
     return TPZ_SUCCESS;
   }
-  void* part = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_get, &w.get_cap, 8 * (tpz::flat_scan_parts_words(n_keys) / 3));
-    if (r != TPZ_SUCCESS) return r;
-    part = w.d_get;
-  }
-  tpz::GetLaunch a{d_tables, n_tables, h_level_first, n_levels, d_keys, d_key_pos, n_keys,
-                   d_result, d_status, d_table, d_block, d_entry, d_val_pos,
-                   static_cast<uint64_t*>(part)};
+  uint64_t* part = nullptr;
+  tpz_err r = ws_buffer(c, stream, kWsGet, 8 * (tpz::flat_scan_parts_words(n_keys) / 3), &part);
+  if (r != TPZ_SUCCESS) return r;
+  tpz::GetLaunch a{f, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels, d_keys,
+                   d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry, d_val_pos,
+                   part};
   tpz::launch_get_walk(a, s);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }
 
-tpz_err tpz_get_values(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
-                       uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
-                       const uint32_t* d_block, const uint32_t* d_entry, const uint64_t* d_val_pos,
-                       uint8_t* d_vals, uint64_t val_cap, void* stream) {
-  if (!c || (n_tables && !d_tables) || (val_cap && !d_vals) ||
+static tpz_err get_values(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                          const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_keys,
+                          const uint8_t* d_result, const uint32_t* d_table, const uint32_t* d_block,
+                          const uint32_t* d_entry, const uint64_t* d_val_pos, uint8_t* d_vals,
+                          uint64_t val_cap, void* stream) {
+  if (!c || (n_tables && !d_tables) || (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
       (n_keys && (!d_result || !d_table || !d_block || !d_entry || !d_val_pos)))
     return TPZ_ERR_INVALID_ARG;
   if (((uintptr_t)d_vals & 15u) || (((uintptr_t)d_tables | (uintptr_t)d_val_pos) & 7u) ||
@@ -1191,16 +1122,131 @@ tpz_err tpz_get_values(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tab
     return TPZ_ERR_INVALID_ARG;
   if (n_keys == 0 || val_cap == 0) return TPZ_SUCCESS;
   TPZ_HIP(hipSetDevice(c->device));
-  tpz::GetGatherLaunch a{d_tables, n_tables, n_keys, d_result, d_table, d_block, d_entry,
-                         d_val_pos, d_vals, val_cap};
+  tpz::GetGatherLaunch a{f, d_runs, n_runs, d_tables, n_tables, n_keys, d_result, d_table, d_block,
+                         d_entry, d_val_pos, d_vals, val_cap};
   tpz::launch_get_gather(a, (hipStream_t)stream);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }
 
-// tpz_lsm_get_keys / tpz_lsm_get_values: d_runs holds n_runs <= TPZ_MEM_MAX_RUNS descriptors.
-static bool runs_ok(const tpz_mem_run* d_runs, uint32_t n_runs) {
-  return n_runs <= TPZ_MEM_MAX_RUNS && (n_runs == 0 || d_runs) && !((uintptr_t)d_runs & 7u);
+// The shape of a scan call. Every flavour: limit >= 1 and n_scans * limit < 2^32 (the hit columns
+// are indexed with it). Then what the merge wave's 64 lanes have to hold, one cursor each:
+//   tables  n_tables <= TPZ_SCAN_MAX_TABLES
+//   lsm     the same, and n_runs + n_tables <= TPZ_SCAN_MAX_TABLES
+//   level   cursors <= TPZ_LEVEL_SCAN_MAX_CURSORS (tpz::level_scan_cursors: runs, L0 tables and
+//           non-empty levels below L0; the entries call has no cursors and passes 0) and any
+//           number of tables
+static bool scan_shape_ok(Flavour f, uint32_t n_runs, uint32_t n_tables, uint64_t cursors,
+                          uint32_t n_scans, uint32_t limit) {
+  if (limit == 0 || (uint64_t)n_scans * limit >= (1ull << 32)) return false;
+  switch (f) {
+    case Flavour::kTables: return n_tables <= TPZ_SCAN_MAX_TABLES;
+    case Flavour::kLsm:
+      return n_tables <= TPZ_SCAN_MAX_TABLES && (uint64_t)n_runs + n_tables <= TPZ_SCAN_MAX_TABLES;
+    case Flavour::kLevel: return cursors <= TPZ_LEVEL_SCAN_MAX_CURSORS;
+  }
+  return false;
+}
+
+// stop_after: 0; the level flavour's diagnostic (tpz_debug_level_scan).
+static tpz_err scan_ranges(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                           const tpz_get_table* d_tables, uint32_t n_tables,
+                           const uint32_t* h_level_first, uint32_t n_levels,
+                           const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
+                           const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
+                           const uint64_t* d_hi_pos, const uint8_t* d_hi_kind, uint32_t n_scans,
+                           uint32_t limit, uint8_t* d_result, uint8_t* d_status, uint32_t* d_where,
+                           uint32_t* d_hit_table, uint32_t* d_hit_block, uint32_t* d_hit_entry,
+                           uint64_t* d_first, uint64_t* d_key_first, uint64_t* d_val_first,
+                           uint64_t* d_info, void* stream, uint32_t stop_after) {
+  if (!c || !d_lo_pos || !d_lo_kind || !d_hi_pos || !d_hi_kind || !d_result || !d_status ||
+      !d_where || !d_hit_table || !d_hit_block || !d_hit_entry || !d_first || !d_key_first ||
+      !d_val_first || !d_info || (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
+    return TPZ_ERR_INVALID_ARG;
+  if (!level_first_ok(h_level_first, n_levels, n_tables)) return TPZ_ERR_INVALID_ARG;
+  const uint64_t cursors =
+      f == Flavour::kLevel ? tpz::level_scan_cursors(h_level_first, n_levels, n_runs) : 0;
+  if (!scan_shape_ok(f, n_runs, n_tables, cursors, n_scans, limit)) return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_tables | (uintptr_t)d_lo_pos | (uintptr_t)d_hi_pos | (uintptr_t)d_first |
+        (uintptr_t)d_key_first | (uintptr_t)d_val_first | (uintptr_t)d_info) & 7u) ||
+      (((uintptr_t)d_where | (uintptr_t)d_hit_table | (uintptr_t)d_hit_block |
+        (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_key_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_val_first, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  tpz_err r = ws_buffer(c, stream, kWsScan,
+                        f == Flavour::kLevel
+                            ? tpz::level_scan_work_bytes(n_scans, (uint32_t)cursors, n_tables)
+                            : tpz::scan_ranges_work_bytes(n_scans, n_runs + n_tables),
+                        &work);
+  if (r != TPZ_SUCCESS) return r;
+  tpz::ScanLaunch a{f, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels, d_lo_keys,
+                    d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit, d_result,
+                    d_status, d_where, d_hit_table, d_hit_block, d_hit_entry, d_first, d_key_first,
+                    d_val_first, d_info, work, stop_after};
+  tpz::launch_scan_ranges(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+static tpz_err scan_entries(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                            const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_scans,
+                            uint32_t limit, const uint32_t* d_hit_table,
+                            const uint32_t* d_hit_block, const uint32_t* d_hit_entry,
+                            const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
+                            uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
+                            void* stream) {
+  if (!c || !d_kpos || !d_vpos || (n_tables && !d_tables) || (key_cap && !d_keys) ||
+      (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
+      (n_scans && (!d_hit_table || !d_hit_block || !d_hit_entry || !d_first)))
+    return TPZ_ERR_INVALID_ARG;
+  if (!scan_shape_ok(f, n_runs, n_tables, 0, n_scans, limit)) return TPZ_ERR_INVALID_ARG;
+  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
+      (((uintptr_t)d_tables | (uintptr_t)d_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u) ||
+      (((uintptr_t)d_hit_table | (uintptr_t)d_hit_block | (uintptr_t)d_hit_entry) & 3u))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_scans == 0) {
+    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
+    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
+    return TPZ_SUCCESS;
+  }
+  void* work = nullptr;
+  tpz_err r = ws_buffer(c, stream, kWsScan, tpz::scan_entries_work_bytes(n_scans), &work);
+  if (r != TPZ_SUCCESS) return r;
+  tpz::ScanEntriesLaunch a{f, d_runs, n_runs, d_tables, n_tables, n_scans, limit, d_hit_table,
+                           d_hit_block, d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals,
+                           val_cap, d_vpos, work};
+  tpz::launch_scan_entries(a, s);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_get_keys(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
+                     const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                     const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                     uint8_t* d_status, uint32_t* d_table, uint32_t* d_block, uint32_t* d_entry,
+                     uint64_t* d_val_pos, void* stream) {
+  return get_keys(Flavour::kTables, c, nullptr, 0, d_tables, n_tables, h_level_first, n_levels,
+                  d_keys, d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry,
+                  d_val_pos, stream);
+}
+
+tpz_err tpz_get_values(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
+                       uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
+                       const uint32_t* d_block, const uint32_t* d_entry, const uint64_t* d_val_pos,
+                       uint8_t* d_vals, uint64_t val_cap, void* stream) {
+  return get_values(Flavour::kTables, c, nullptr, 0, d_tables, n_tables, n_keys, d_result, d_table,
+                    d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
 }
 
 tpz_err tpz_mem_prefix(tpz_ctx* c, const tpz_entries* entries, uint64_t* d_prefix, void* stream) {
@@ -1221,34 +1267,9 @@ tpz_err tpz_lsm_get_keys(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
                          const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
                          uint8_t* d_status, uint32_t* d_table, uint32_t* d_block,
                          uint32_t* d_entry, uint64_t* d_val_pos, void* stream) {
-  if (!c || !d_key_pos || !d_result || !d_status || !d_table || !d_block || !d_entry || !d_val_pos ||
-      (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
-    return TPZ_ERR_INVALID_ARG;
-  if (!level_first_ok(h_level_first, n_levels, n_tables) || n_keys == 0xFFFFFFFFu)
-    return TPZ_ERR_INVALID_ARG;
-  if ((((uintptr_t)d_tables | (uintptr_t)d_key_pos | (uintptr_t)d_val_pos) & 7u) ||
-      (((uintptr_t)d_table | (uintptr_t)d_block | (uintptr_t)d_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n_keys == 0) {
-    TPZ_HIP(hipMemsetAsync(d_val_pos, 0, 8, s));
-    return TPZ_SUCCESS;
-  }
-  void* part = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_get, &w.get_cap, 8 * (tpz::flat_scan_parts_words(n_keys) / 3));
-    if (r != TPZ_SUCCESS) return r;
-    part = w.d_get;
-  }
-  tpz::LsmGetLaunch a{{d_tables, n_tables, h_level_first, n_levels, d_keys, d_key_pos, n_keys,
-                       d_result, d_status, d_table, d_block, d_entry, d_val_pos,
-                       static_cast<uint64_t*>(part)}, d_runs, n_runs};
-  tpz::launch_lsm_get_walk(a, s);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
+  return get_keys(Flavour::kLsm, c, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels,
+                  d_keys, d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry,
+                  d_val_pos, stream);
 }
 
 tpz_err tpz_lsm_get_values(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
@@ -1257,25 +1278,8 @@ tpz_err tpz_lsm_get_values(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_run
                            const uint32_t* d_block, const uint32_t* d_entry,
                            const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
                            void* stream) {
-  if (!c || (n_tables && !d_tables) || (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
-      (n_keys && (!d_result || !d_table || !d_block || !d_entry || !d_val_pos)))
-    return TPZ_ERR_INVALID_ARG;
-  if (((uintptr_t)d_vals & 15u) || (((uintptr_t)d_tables | (uintptr_t)d_val_pos) & 7u) ||
-      (((uintptr_t)d_table | (uintptr_t)d_block | (uintptr_t)d_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  if (n_keys == 0 || val_cap == 0) return TPZ_SUCCESS;
-  TPZ_HIP(hipSetDevice(c->device));
-  tpz::LsmGetGatherLaunch a{{d_tables, n_tables, n_keys, d_result, d_table, d_block, d_entry,
-                             d_val_pos, d_vals, val_cap}, d_runs, n_runs};
-  tpz::launch_lsm_get_gather(a, (hipStream_t)stream);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
-}
-
-// limit >= 1 and n_scans * limit < 2^32 (the hit columns are indexed with it).
-static bool scan_shape_ok(uint32_t n_tables, uint32_t n_scans, uint32_t limit) {
-  return n_tables <= TPZ_SCAN_MAX_TABLES && limit != 0 &&
-         (uint64_t)n_scans * limit < (1ull << 32);
+  return get_values(Flavour::kLsm, c, d_runs, n_runs, d_tables, n_tables, n_keys, d_result,
+                    d_table, d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
 }
 
 tpz_err tpz_scan_ranges(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
@@ -1287,42 +1291,10 @@ tpz_err tpz_scan_ranges(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_ta
                         uint32_t* d_hit_table, uint32_t* d_hit_block, uint32_t* d_hit_entry,
                         uint64_t* d_first, uint64_t* d_key_first, uint64_t* d_val_first,
                         uint64_t* d_info, void* stream) {
-  if (!c || !d_lo_pos || !d_lo_kind || !d_hi_pos || !d_hi_kind || !d_result || !d_status ||
-      !d_where || !d_hit_table || !d_hit_block || !d_hit_entry || !d_first || !d_key_first ||
-      !d_val_first || !d_info || (n_tables && !d_tables))
-    return TPZ_ERR_INVALID_ARG;
-  if (!scan_shape_ok(n_tables, n_scans, limit) ||
-      !level_first_ok(h_level_first, n_levels, n_tables))
-    return TPZ_ERR_INVALID_ARG;
-  if ((((uintptr_t)d_tables | (uintptr_t)d_lo_pos | (uintptr_t)d_hi_pos | (uintptr_t)d_first |
-        (uintptr_t)d_key_first | (uintptr_t)d_val_first | (uintptr_t)d_info) & 7u) ||
-      (((uintptr_t)d_where | (uintptr_t)d_hit_table | (uintptr_t)d_hit_block |
-        (uintptr_t)d_hit_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n_scans == 0) {
-    TPZ_HIP(hipMemsetAsync(d_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_key_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_val_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
-    return TPZ_SUCCESS;
-  }
-  void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_ranges_work_bytes(n_scans, n_tables));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_scan;
-  }
-  tpz::ScanLaunch a{d_tables, n_tables, n_levels ? h_level_first[1] : 0u, d_lo_keys, d_lo_pos,
-                    d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit, d_result, d_status,
-                    d_where, d_hit_table, d_hit_block, d_hit_entry, d_first, d_key_first,
-                    d_val_first, d_info, work};
-  tpz::launch_scan_ranges(a, s);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
+  return scan_ranges(Flavour::kTables, c, nullptr, 0, d_tables, n_tables, h_level_first, n_levels,
+                     d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit,
+                     d_result, d_status, d_where, d_hit_table, d_hit_block, d_hit_entry, d_first,
+                     d_key_first, d_val_first, d_info, stream, 0);
 }
 
 tpz_err tpz_scan_entries(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,
@@ -1331,36 +1303,9 @@ tpz_err tpz_scan_entries(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_t
                          const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
                          uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
                          void* stream) {
-  if (!c || !d_kpos || !d_vpos || (n_tables && !d_tables) || (key_cap && !d_keys) ||
-      (val_cap && !d_vals) ||
-      (n_scans && (!d_hit_table || !d_hit_block || !d_hit_entry || !d_first)))
-    return TPZ_ERR_INVALID_ARG;
-  if (!scan_shape_ok(n_tables, n_scans, limit)) return TPZ_ERR_INVALID_ARG;
-  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
-      (((uintptr_t)d_tables | (uintptr_t)d_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u) ||
-      (((uintptr_t)d_hit_table | (uintptr_t)d_hit_block | (uintptr_t)d_hit_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n_scans == 0) {
-    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
-    return TPZ_SUCCESS;
-  }
-  void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_entries_work_bytes(n_scans));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_scan;
-  }
-  tpz::ScanEntriesLaunch a{d_tables, n_tables, n_scans, limit, d_hit_table, d_hit_block,
-                           d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals, val_cap, d_vpos,
-                           work};
-  tpz::launch_scan_entries(a, s);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
+  return scan_entries(Flavour::kTables, c, nullptr, 0, d_tables, n_tables, n_scans, limit,
+                      d_hit_table, d_hit_block, d_hit_entry, d_first, d_keys, key_cap, d_kpos,
+                      d_vals, val_cap, d_vpos, stream);
 }
 
 tpz_err tpz_lsm_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
@@ -1373,43 +1318,10 @@ tpz_err tpz_lsm_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_ru
                             uint32_t* d_where, uint32_t* d_hit_table, uint32_t* d_hit_block,
                             uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
                             uint64_t* d_val_first, uint64_t* d_info, void* stream) {
-  if (!c || !d_lo_pos || !d_lo_kind || !d_hi_pos || !d_hi_kind || !d_result || !d_status ||
-      !d_where || !d_hit_table || !d_hit_block || !d_hit_entry || !d_first || !d_key_first ||
-      !d_val_first || !d_info || (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
-    return TPZ_ERR_INVALID_ARG;
-  if (!scan_shape_ok(n_tables, n_scans, limit) || n_runs + n_tables > TPZ_SCAN_MAX_TABLES ||
-      !level_first_ok(h_level_first, n_levels, n_tables))
-    return TPZ_ERR_INVALID_ARG;
-  if ((((uintptr_t)d_tables | (uintptr_t)d_lo_pos | (uintptr_t)d_hi_pos | (uintptr_t)d_first |
-        (uintptr_t)d_key_first | (uintptr_t)d_val_first | (uintptr_t)d_info) & 7u) ||
-      (((uintptr_t)d_where | (uintptr_t)d_hit_table | (uintptr_t)d_hit_block |
-        (uintptr_t)d_hit_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n_scans == 0) {
-    TPZ_HIP(hipMemsetAsync(d_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_key_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_val_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
-    return TPZ_SUCCESS;
-  }
-  void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap,
-                     tpz::scan_ranges_work_bytes(n_scans, n_runs + n_tables));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_scan;
-  }
-  tpz::LsmScanLaunch a{{d_tables, n_tables, n_levels ? h_level_first[1] : 0u, d_lo_keys, d_lo_pos,
-                        d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit, d_result,
-                        d_status, d_where, d_hit_table, d_hit_block, d_hit_entry, d_first,
-                        d_key_first, d_val_first, d_info, work}, d_runs, n_runs};
-  tpz::launch_lsm_scan_ranges(a, s);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
+  return scan_ranges(Flavour::kLsm, c, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels,
+                     d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit,
+                     d_result, d_status, d_where, d_hit_table, d_hit_block, d_hit_entry, d_first,
+                     d_key_first, d_val_first, d_info, stream, 0);
 }
 
 tpz_err tpz_lsm_scan_entries(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
@@ -1419,96 +1331,9 @@ tpz_err tpz_lsm_scan_entries(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_r
                              const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
                              uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
                              void* stream) {
-  if (!c || !d_kpos || !d_vpos || (n_tables && !d_tables) || (key_cap && !d_keys) ||
-      (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
-      (n_scans && (!d_hit_table || !d_hit_block || !d_hit_entry || !d_first)))
-    return TPZ_ERR_INVALID_ARG;
-  if (!scan_shape_ok(n_tables, n_scans, limit) || n_runs + n_tables > TPZ_SCAN_MAX_TABLES)
-    return TPZ_ERR_INVALID_ARG;
-  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
-      (((uintptr_t)d_tables | (uintptr_t)d_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u) ||
-      (((uintptr_t)d_hit_table | (uintptr_t)d_hit_block | (uintptr_t)d_hit_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n_scans == 0) {
-    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
-    return TPZ_SUCCESS;
-  }
-  void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_entries_work_bytes(n_scans));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_scan;
-  }
-  tpz::LsmScanEntriesLaunch a{{d_tables, n_tables, n_scans, limit, d_hit_table, d_hit_block,
-                               d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals, val_cap,
-                               d_vpos, work}, d_runs, n_runs};
-  tpz::launch_lsm_scan_entries(a, s);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
-}
-
-// tpz_level_scan_ranges / tpz_level_scan_entries: any number of tables; the merge wave's lanes go
-// to the cursors (runs, L0 tables, non-empty levels below L0).
-static bool level_scan_shape_ok(uint32_t n_scans, uint32_t limit) {
-  return limit != 0 && (uint64_t)n_scans * limit < (1ull << 32);
-}
-
-static tpz_err level_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
-                                 const tpz_get_table* d_tables, uint32_t n_tables,
-                                 const uint32_t* h_level_first, uint32_t n_levels,
-                                 const uint8_t* d_lo_keys, const uint64_t* d_lo_pos,
-                                 const uint8_t* d_lo_kind, const uint8_t* d_hi_keys,
-                                 const uint64_t* d_hi_pos, const uint8_t* d_hi_kind,
-                                 uint32_t n_scans, uint32_t limit, uint8_t* d_result,
-                                 uint8_t* d_status, uint32_t* d_where, uint32_t* d_hit_table,
-                                 uint32_t* d_hit_block, uint32_t* d_hit_entry, uint64_t* d_first,
-                                 uint64_t* d_key_first, uint64_t* d_val_first, uint64_t* d_info,
-                                 void* stream, uint32_t stop_after) {
-  if (!c || !d_lo_pos || !d_lo_kind || !d_hi_pos || !d_hi_kind || !d_result || !d_status ||
-      !d_where || !d_hit_table || !d_hit_block || !d_hit_entry || !d_first || !d_key_first ||
-      !d_val_first || !d_info || (n_tables && !d_tables) || !runs_ok(d_runs, n_runs))
-    return TPZ_ERR_INVALID_ARG;
-  if (!level_scan_shape_ok(n_scans, limit) || !level_first_ok(h_level_first, n_levels, n_tables))
-    return TPZ_ERR_INVALID_ARG;
-  const uint64_t cursors = tpz::level_scan_cursors(h_level_first, n_levels, n_runs);
-  if (cursors > TPZ_LEVEL_SCAN_MAX_CURSORS) return TPZ_ERR_INVALID_ARG;
-  const uint32_t n_cur = (uint32_t)cursors;
-  if ((((uintptr_t)d_tables | (uintptr_t)d_lo_pos | (uintptr_t)d_hi_pos | (uintptr_t)d_first |
-        (uintptr_t)d_key_first | (uintptr_t)d_val_first | (uintptr_t)d_info) & 7u) ||
-      (((uintptr_t)d_where | (uintptr_t)d_hit_table | (uintptr_t)d_hit_block |
-        (uintptr_t)d_hit_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n_scans == 0) {
-    TPZ_HIP(hipMemsetAsync(d_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_key_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_val_first, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_info, 0, 24, s));
-    return TPZ_SUCCESS;
-  }
-  void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap,
-                     tpz::level_scan_work_bytes(n_scans, n_cur, n_tables));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_scan;
-  }
-  tpz::LevelScanLaunch a{{{d_tables, n_tables, n_levels ? h_level_first[1] : 0u, d_lo_keys,
-                           d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans, limit,
-                           d_result, d_status, d_where, d_hit_table, d_hit_block, d_hit_entry,
-                           d_first, d_key_first, d_val_first, d_info, work}, d_runs, n_runs},
-                         h_level_first, n_levels, stop_after};
-  tpz::launch_level_scan_ranges(a, s);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
+  return scan_entries(Flavour::kLsm, c, d_runs, n_runs, d_tables, n_tables, n_scans, limit,
+                      d_hit_table, d_hit_block, d_hit_entry, d_first, d_keys, key_cap, d_kpos,
+                      d_vals, val_cap, d_vpos, stream);
 }
 
 tpz_err tpz_level_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
@@ -1521,10 +1346,10 @@ tpz_err tpz_level_scan_ranges(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_
                               uint32_t* d_where, uint32_t* d_hit_table, uint32_t* d_hit_block,
                               uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
                               uint64_t* d_val_first, uint64_t* d_info, void* stream) {
-  return level_scan_ranges(c, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels,
-                           d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans,
-                           limit, d_result, d_status, d_where, d_hit_table, d_hit_block,
-                           d_hit_entry, d_first, d_key_first, d_val_first, d_info, stream, 0);
+  return scan_ranges(Flavour::kLevel, c, d_runs, n_runs, d_tables, n_tables, h_level_first,
+                     n_levels, d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind,
+                     n_scans, limit, d_result, d_status, d_where, d_hit_table, d_hit_block,
+                     d_hit_entry, d_first, d_key_first, d_val_first, d_info, stream, 0);
 }
 
 // Diagnostic (not in tpz_gpu.h; tools/levelscan_probe.py): tpz_level_scan_ranges cut short, 1 =
@@ -1537,11 +1362,10 @@ extern "C" tpz_err tpz_debug_level_scan(
     uint8_t* d_result, uint8_t* d_status, uint32_t* d_where, uint32_t* d_hit_table,
     uint32_t* d_hit_block, uint32_t* d_hit_entry, uint64_t* d_first, uint64_t* d_key_first,
     uint64_t* d_val_first, uint64_t* d_info, void* stream, uint32_t stop_after) {
-  return level_scan_ranges(c, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels,
-                           d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind, n_scans,
-                           limit, d_result, d_status, d_where, d_hit_table, d_hit_block,
-                           d_hit_entry, d_first, d_key_first, d_val_first, d_info, stream,
-                           stop_after);
+  return scan_ranges(Flavour::kLevel, c, d_runs, n_runs, d_tables, n_tables, h_level_first,
+                     n_levels, d_lo_keys, d_lo_pos, d_lo_kind, d_hi_keys, d_hi_pos, d_hi_kind,
+                     n_scans, limit, d_result, d_status, d_where, d_hit_table, d_hit_block,
+                     d_hit_entry, d_first, d_key_first, d_val_first, d_info, stream, stop_after);
 }
 
 tpz_err tpz_level_scan_entries(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
@@ -1551,36 +1375,9 @@ tpz_err tpz_level_scan_entries(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n
                                const uint64_t* d_first, uint8_t* d_keys, uint64_t key_cap,
                                uint64_t* d_kpos, uint8_t* d_vals, uint64_t val_cap,
                                uint64_t* d_vpos, void* stream) {
-  if (!c || !d_kpos || !d_vpos || (n_tables && !d_tables) || (key_cap && !d_keys) ||
-      (val_cap && !d_vals) || !runs_ok(d_runs, n_runs) ||
-      (n_scans && (!d_hit_table || !d_hit_block || !d_hit_entry || !d_first)))
-    return TPZ_ERR_INVALID_ARG;
-  if (!level_scan_shape_ok(n_scans, limit)) return TPZ_ERR_INVALID_ARG;
-  if ((((uintptr_t)d_keys | (uintptr_t)d_vals) & 15u) ||
-      (((uintptr_t)d_tables | (uintptr_t)d_first | (uintptr_t)d_kpos | (uintptr_t)d_vpos) & 7u) ||
-      (((uintptr_t)d_hit_table | (uintptr_t)d_hit_block | (uintptr_t)d_hit_entry) & 3u))
-    return TPZ_ERR_INVALID_ARG;
-  TPZ_HIP(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n_scans == 0) {
-    TPZ_HIP(hipMemsetAsync(d_kpos, 0, 8, s));
-    TPZ_HIP(hipMemsetAsync(d_vpos, 0, 8, s));
-    return TPZ_SUCCESS;
-  }
-  void* work = nullptr;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_scan, &w.scan_cap, tpz::scan_entries_work_bytes(n_scans));
-    if (r != TPZ_SUCCESS) return r;
-    work = w.d_scan;
-  }
-  tpz::LsmScanEntriesLaunch a{{d_tables, n_tables, n_scans, limit, d_hit_table, d_hit_block,
-                               d_hit_entry, d_first, d_keys, key_cap, d_kpos, d_vals, val_cap,
-                               d_vpos, work}, d_runs, n_runs};
-  tpz::launch_lsm_scan_entries(a, s);
-  TPZ_HIP(hipGetLastError());
-  return TPZ_SUCCESS;
+  return scan_entries(Flavour::kLevel, c, d_runs, n_runs, d_tables, n_tables, n_scans, limit,
+                      d_hit_table, d_hit_block, d_hit_entry, d_first, d_keys, key_cap, d_kpos,
+                      d_vals, val_cap, d_vpos, stream);
 }
 
 tpz_err tpz_flat_entry_pos(tpz_ctx* c, const tpz_flat_columns* cols, uint32_t n_blocks,
@@ -1677,11 +1474,9 @@ tpz_err tpz_sst_finish(tpz_ctx* c, const tpz_entries* en, const tpz_sst_image* d
   uint32_t* acc = nullptr;
   {
     std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_tables, &w.tables_cap, bytes);
-    if (r == TPZ_SUCCESS) r = get_acc(c, stream, n_ranges, &acc);
+    tpz_err r = grow(c, stream, kWsTables, bytes, &work);
+    if (r == TPZ_SUCCESS) r = grow(c, stream, kWsAcc, (size_t)n_ranges * 4, &acc);
     if (r != TPZ_SUCCESS) return r;
-    work = static_cast<uint64_t*>(w.d_tables);
   }
   tpz::FinishLaunch a{};
   a.keys = en->d_keys;
@@ -1815,16 +1610,13 @@ tpz_err tpz_table_runs_layout(tpz_ctx* c, const tpz_table* d_tables, uint32_t n_
   if (!block_first_ok(h_block_first, n_runs)) return TPZ_ERR_INVALID_ARG;
   TPZ_HIP(hipSetDevice(c->device));
   const uint32_t nb = h_block_first[n_runs];
-  void* part = nullptr;
+  uint64_t* part = nullptr;
   if (nb) {
-    std::lock_guard<std::mutex> g(c->mu);
-    tpz_workspace& w = c->ws[stream];
-    tpz_err r = grow(stream, &w.d_runs, &w.runs_cap, 8 * tpz::flat_scan_parts_words(nb));
+    tpz_err r = ws_buffer(c, stream, kWsRuns, 8 * tpz::flat_scan_parts_words(nb), &part);
     if (r != TPZ_SUCCESS) return r;
-    part = w.d_runs;
   }
   tpz::launch_table_runs_layout(d_tables, n_runs, h_block_first, d_block_first, d_run_first, d_info,
-                                static_cast<uint64_t*>(part), (hipStream_t)stream);
+                                part, (hipStream_t)stream);
   TPZ_HIP(hipGetLastError());
   return TPZ_SUCCESS;
 }

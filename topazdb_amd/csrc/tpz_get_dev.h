@@ -51,6 +51,11 @@ struct GatherParams {
   u64 val_cap;
 };
 
+// Host side: lsm_get_walk_kernel lives in tpz_mem.hip, so launch_get_walk (tpz_get.hip), which
+// fills `w` for both flavours, launches it through this.
+void launch_lsm_walk_kernel(const WalkParams& w, const tpz_mem_run* runs, u32 n_runs, dim3 grid,
+                            hipStream_t stream);
+
 // What a query reports (tpz_get_keys' columns for it).
 struct WalkOut {
   u32 res, st, tb, blk, ent;

@@ -376,8 +376,19 @@ struct WalEntriesLaunch {
 uint64_t wal_entries_work_bytes(uint32_t n);
 hipError_t launch_wal_entries(const WalEntriesLaunch& a, hipStream_t stream);
 
-// tpz_get_keys / tpz_get_values (tpz_get.hip): LevelController::get over resident tables.
+// Which query call a launch serves: the tables alone (tpz_get_* / tpz_scan_*), memtable runs in
+// front of them (tpz_lsm_*), or runs plus one merge cursor per level (tpz_level_scan_*). It picks
+// the kernels and is never inferred from n_runs: the lsm kernels run with no runs too (they apply
+// LsmStorage::get's empty-key assert, which tpz_get_keys does not).
+enum class Flavour : uint32_t { kTables, kLsm, kLevel };
+
+// tpz_get_keys / tpz_get_values / tpz_lsm_get_keys / tpz_lsm_get_values (tpz_get.hip; the lsm
+// walk's kernel is tpz_mem.hip's): LevelController::get over resident tables, and LsmStorage::get
+// over memtable runs plus them.
 struct GetLaunch {
+  Flavour flavour;              // kTables / kLsm
+  const tpz_mem_run* runs;      // device (kLsm)
+  uint32_t n_runs;              // <= TPZ_MEM_MAX_RUNS
   const tpz_get_table* tabs;    // device
   uint32_t n_tables;
   const uint32_t* level_first;  // host: n_levels + 1, checked by the caller
@@ -395,6 +406,9 @@ struct GetLaunch {
 };
 void launch_get_walk(const GetLaunch& a, hipStream_t stream);
 struct GetGatherLaunch {
+  Flavour flavour;              // kTables / kLsm
+  const tpz_mem_run* runs;
+  uint32_t n_runs;
   const tpz_get_table* tabs;
   uint32_t n_tables;
   uint32_t n_q;                 // > 0
@@ -408,28 +422,21 @@ struct GetGatherLaunch {
 };
 void launch_get_gather(const GetGatherLaunch& a, hipStream_t stream);
 
-// tpz_mem_prefix / tpz_lsm_get_keys / tpz_lsm_get_values (tpz_mem.hip): memtable runs resident in
-// HBM, and LsmStorage::get over them plus the tables.
+// tpz_mem_prefix (tpz_mem.hip): the prefix column of a memtable run resident in HBM.
 void launch_mem_prefix(const tpz_entries& e, uint64_t* prefix, hipStream_t stream);   // n_entries > 0
-struct LsmGetLaunch {
-  GetLaunch get;
-  const tpz_mem_run* runs;      // device
-  uint32_t n_runs;              // <= TPZ_MEM_MAX_RUNS
-};
-void launch_lsm_get_walk(const LsmGetLaunch& a, hipStream_t stream);
-struct LsmGetGatherLaunch {
-  GetGatherLaunch get;
-  const tpz_mem_run* runs;
-  uint32_t n_runs;
-};
-void launch_lsm_get_gather(const LsmGetGatherLaunch& a, hipStream_t stream);
 
-// tpz_scan_ranges / tpz_scan_entries (tpz_scan.hip): LsmStorage::scan's SST half over resident
-// tables.
+// tpz_scan_ranges / tpz_lsm_scan_ranges (tpz_scan.hip) and tpz_level_scan_ranges
+// (tpz_levelscan.hip): LsmStorage::scan over resident tables; kLsm and kLevel put the memtable
+// runs' cursors in front of the tables', kLevel takes one cursor per run, per L0 table and per
+// non-empty level below L0.
 struct ScanLaunch {
+  Flavour flavour;
+  const tpz_mem_run* runs;      // device (kLsm, kLevel)
+  uint32_t n_runs;              // <= TPZ_MEM_MAX_RUNS; kLsm: n_runs + n_tables <= TPZ_SCAN_MAX_TABLES
   const tpz_get_table* tabs;    // device
-  uint32_t n_tables;            // <= TPZ_SCAN_MAX_TABLES
-  uint32_t l0;                  // the number of L0 tables (h_level_first[1], or 0)
+  uint32_t n_tables;            // <= TPZ_SCAN_MAX_TABLES; kLevel: any number
+  const uint32_t* level_first;  // host: n_levels + 1, checked by the caller
+  uint32_t n_levels;
   const uint8_t* lo;
   const uint64_t* lo_pos;
   const uint8_t* lo_kind;
@@ -448,11 +455,26 @@ struct ScanLaunch {
   uint64_t* key_first;
   uint64_t* val_first;
   uint64_t* info;               // 3 u64
-  void* work;                   // scan_ranges_work_bytes(n_scans, n_tables) of device scratch
+  void* work;                   // device scratch: scan_ranges_work_bytes(n_scans, n_runs +
+                                // n_tables); kLevel: level_scan_work_bytes(n_scans,
+                                // level_scan_cursors(..), n_tables)
+  uint32_t stop_after;          // 0; kLevel diagnostic: 1 ends after the index pass, 2 after the links
+  uint32_t l0() const { return n_levels ? level_first[1] : 0u; }   // the number of L0 tables
 };
-uint64_t scan_ranges_work_bytes(uint32_t n_scans, uint32_t n_tables);
+uint64_t scan_ranges_work_bytes(uint32_t n_scans, uint32_t n_cursors);
+uint64_t level_scan_cursors(const uint32_t* level_first, uint32_t n_levels, uint32_t n_runs);
+uint64_t level_scan_work_bytes(uint32_t n_scans, uint32_t n_cursors, uint32_t n_tables);
+// Every flavour (kLevel: through launch_level_scan_ranges).
 void launch_scan_ranges(const ScanLaunch& a, hipStream_t stream);
+void launch_level_scan_ranges(const ScanLaunch& a, hipStream_t stream);
+// The scans of d_first / d_key_first / d_val_first and d_info (the tail of both).
+void launch_scan_totals(const ScanLaunch& a, uint64_t* part, hipStream_t stream);
+// tpz_scan_entries / tpz_lsm_scan_entries / tpz_level_scan_entries (tpz_scan.hip): the gather of
+// the hits; kLsm and kLevel take the same kernels (hits in runs as well as in tables).
 struct ScanEntriesLaunch {
+  Flavour flavour;
+  const tpz_mem_run* runs;
+  uint32_t n_runs;
   const tpz_get_table* tabs;
   uint32_t n_tables;
   uint32_t n_scans;             // > 0
@@ -471,35 +493,6 @@ struct ScanEntriesLaunch {
 };
 uint64_t scan_entries_work_bytes(uint32_t n_scans);
 void launch_scan_entries(const ScanEntriesLaunch& a, hipStream_t stream);
-// The scans of d_first / d_key_first / d_val_first and d_info (the tail of launch_scan_ranges).
-void launch_scan_totals(const ScanLaunch& a, uint64_t* part, hipStream_t stream);
-// tpz_lsm_scan_ranges / tpz_lsm_scan_entries (tpz_mem.hip): LsmStorage::scan whole, the memtable
-// runs' cursors in front of the tables'. work: scan_ranges_work_bytes(n_scans, n_runs + n_tables)
-// / scan_entries_work_bytes(n_scans).
-struct LsmScanLaunch {
-  ScanLaunch scan;
-  const tpz_mem_run* runs;      // device
-  uint32_t n_runs;              // <= TPZ_MEM_MAX_RUNS, n_runs + n_tables <= TPZ_SCAN_MAX_TABLES
-};
-void launch_lsm_scan_ranges(const LsmScanLaunch& a, hipStream_t stream);
-struct LsmScanEntriesLaunch {
-  ScanEntriesLaunch scan;
-  const tpz_mem_run* runs;
-  uint32_t n_runs;
-};
-void launch_lsm_scan_entries(const LsmScanEntriesLaunch& a, hipStream_t stream);
-// tpz_level_scan_ranges (tpz_levelscan.hip): the same scan with one cursor per run, per L0 table
-// and per non-empty level below L0. work: level_scan_work_bytes(n_scans, level_scan_cursors(..),
-// n_tables) of device scratch. (tpz_level_scan_entries is launch_lsm_scan_entries.)
-struct LevelScanLaunch {
-  LsmScanLaunch lsm;            // n_tables: any number
-  const uint32_t* level_first;  // host: n_levels + 1, checked by the caller
-  uint32_t n_levels;
-  uint32_t stop_after;          // 0; diagnostic: 1 ends after the index pass, 2 after the links
-};
-uint64_t level_scan_cursors(const uint32_t* level_first, uint32_t n_levels, uint32_t n_runs);
-uint64_t level_scan_work_bytes(uint32_t n_scans, uint32_t n_cursors, uint32_t n_tables);
-void launch_level_scan_ranges(const LevelScanLaunch& a, hipStream_t stream);
 
 // tpz_entries_bound / tpz_table_cut / tpz_sst_finish (tpz_tables.hip): a compaction task's key
 // ranges, table cuts and SST file images.

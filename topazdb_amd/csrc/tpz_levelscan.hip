@@ -1,7 +1,8 @@
 // tpz_levelscan.hip — gfx950 kernels of the level scan (tpz_level_scan_ranges; include/tpz_gpu.h):
 // LsmStorage::scan (src/lsm_storage.rs:335-374) over memtable runs plus resident tables with one
 // merge cursor per run, per L0 table and per non-empty level below L0, so a level may hold any
-// number of tables. tpz_level_scan_entries is tpz_mem.hip's gather (launch_lsm_scan_entries).
+// number of tables. launch_scan_ranges (tpz_scan.hip) hands the level flavour's ScanLaunch on to
+// launch_level_scan_ranges here; tpz_level_scan_entries is tpz_scan.hip's gather with the runs.
 //
 //   level_index_kernel   One thread per table, once per call: can the reference open it and its
 //                        biggest key (table.rs:143-151), and its head records (tpz_levelscan_dev.h).
@@ -65,7 +66,6 @@ __global__ __launch_bounds__(256) void level_merge_kernel(LevelMergeParams p) {
   scandev::merge_body<true, true>(p.s, p.m, p.lv);
 }
 
-uint64_t up8(uint64_t x) { return (x + 7) & ~7ull; }
 uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 }  // namespace
@@ -77,22 +77,20 @@ uint64_t level_scan_cursors(const uint32_t* level_first, uint32_t n_levels, uint
 }
 
 uint64_t level_scan_work_bytes(uint32_t n_scans, uint32_t n_cursors, uint32_t n_tables) {
-  const uint64_t cells = (uint64_t)n_scans * n_cursors;
-  return up16(sizeof(TabIndex) * (uint64_t)n_tables) + 16 * (uint64_t)n_tables + 16 + 16 * cells +
-         up8(cells) + 8 * (flat_scan_parts_words(n_scans) / 3);
+  return up16(sizeof(TabIndex) * (uint64_t)n_tables) + 16 * (uint64_t)n_tables + 16 +
+         scandev::cursor_work_bytes(n_scans, (uint64_t)n_scans * n_cursors, 4);
 }
 
-void launch_level_scan_ranges(const LevelScanLaunch& l, hipStream_t stream) {
-  const ScanLaunch& a = l.lsm.scan;
+void launch_level_scan_ranges(const ScanLaunch& a, hipStream_t stream) {
   Shape sh{};
   sh.tabs = a.tabs;
   sh.n_tables = a.n_tables;
-  sh.l0 = a.l0;
-  sh.cf[0] = a.l0;
-  for (u32 lv = 1; lv < l.n_levels; lv++)
-    if (l.level_first[lv + 1] > l.level_first[lv]) sh.cf[++sh.n_lv] = l.level_first[lv + 1];
+  sh.l0 = a.l0();
+  sh.cf[0] = a.l0();
+  for (u32 lv = 1; lv < a.n_levels; lv++)
+    if (a.level_first[lv + 1] > a.level_first[lv]) sh.cf[++sh.n_lv] = a.level_first[lv + 1];
   for (u32 k = sh.n_lv + 1; k <= TPZ_GET_MAX_LEVELS; k++) sh.cf[k] = a.n_tables;
-  const u32 n_cur = l.lsm.n_runs + a.l0 + sh.n_lv;
+  const u32 n_cur = a.n_runs + a.l0() + sh.n_lv;
   const uint64_t cells = (uint64_t)a.n_scans * n_cur;
 
   uint8_t* w = static_cast<uint8_t*>(a.work);
@@ -103,33 +101,27 @@ void launch_level_scan_ranges(const LevelScanLaunch& l, hipStream_t stream) {
   w += 16 * (uint64_t)a.n_tables;
   u32* first_unopened = reinterpret_cast<u32*>(w);
   w += 16;                                       // (the cursors are read 16 bytes at a time)
-  u32* cur = reinterpret_cast<u32*>(w);
-  w += 16 * cells;
-  uint8_t* cst = w;
-  u64* part = reinterpret_cast<u64*>(w + up8(cells));
+  const scandev::CursorWork cw = scandev::carve_cursors(w, cells, 4);
 
   if (a.n_tables)
     hipLaunchKernelGGL(level_index_kernel, dim3((a.n_tables + 255) / 256), dim3(256), 0, stream, sh,
                        idx);
-  if (l.stop_after == 1) return;
+  if (a.stop_after == 1) return;
   hipLaunchKernelGGL(level_links_kernel, dim3(sh.n_lv + 1), dim3(64), 0, stream, sh, idx, nf, nv,
                      first_unopened);
-  if (l.stop_after == 2) return;
-  const scandev::Runs m{l.lsm.runs, l.lsm.n_runs};
+  if (a.stop_after == 2) return;
+  const scandev::Runs m{a.runs, a.n_runs};
   const Levels lv{a.tabs, a.n_tables, idx, nf, nv, first_unopened, n_cur};
   if (cells) {
-    LevelSeekParams s{{a.tabs, a.n_tables, a.l0, a.lo, a.lo_pos, a.lo_kind, a.hi, a.hi_pos,
-                       a.hi_kind, a.n_scans, cur, cst}, m, sh, lv};
+    const LevelSeekParams s{scandev::seek_params(a, cw), m, sh, lv};
     hipLaunchKernelGGL(level_seek_kernel, dim3((u32)((cells + 255) / 256)), dim3(256), 0, stream,
                        s);
   }
-  LevelMergeParams mp{{a.tabs, a.n_tables, a.l0, a.hi, a.hi_pos, a.lo_kind, a.hi_kind, a.n_scans,
-                       a.limit, cur, cst, a.result, a.status, a.where, a.hit_table, a.hit_block,
-                       a.hit_entry, a.first, a.key_first, a.val_first}, m, lv};
+  const LevelMergeParams mp{scandev::merge_params(a, cw), m, lv};
   hipLaunchKernelGGL(level_merge_kernel,
                      dim3((a.n_scans + scandev::kWaves - 1) / scandev::kWaves), dim3(256), 0, stream,
                      mp);
-  launch_scan_totals(a, part, stream);
+  launch_scan_totals(a, cw.part, stream);
 }
 
 }  // namespace tpz

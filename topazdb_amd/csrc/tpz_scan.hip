@@ -1,5 +1,8 @@
-// tpz_scan.hip — gfx950 kernels of the batched LsmStorage::scan (src/lsm_storage.rs:335-374, its
-// SST half) over tables resident in HBM (tpz_scan_ranges, tpz_scan_entries; include/tpz_gpu.h).
+// tpz_scan.hip — gfx950 kernels of the batched LsmStorage::scan (src/lsm_storage.rs:335-374) over
+// tables resident in HBM: its SST half (tpz_scan_ranges, tpz_scan_entries; include/tpz_gpu.h) and
+// the whole scan, memtable runs merged in (tpz_lsm_scan_ranges, tpz_lsm_scan_entries;
+// tpz_level_scan_entries is the same gather). One launcher per operation picks the kernels by
+// flavour; the level flavour's ranges call goes on to tpz_levelscan.hip.
 //
 //   scan_seek_kernel     One thread per (scan, table), the threads of a scan adjacent in priority
 //                        order (L0 newest first, then the levels as stored: level.rs:538-579). It
@@ -26,6 +29,12 @@
 //                        and copies keys and values in 16-byte pieces of the destination
 //                        (tpz_copy.h, as get_gather_kernel): by their own lane up to kLaneCopyMax
 //                        bytes, longer ones by the whole wave.
+//   lsm_scan_*_kernel    The same three kernels with the memtable side, from the same bodies
+//                        (tpz_scan_dev.h, kMem): the seek pass also bisects every run twice per
+//                        scan (map.range's two ends), the merge gives lanes 0 .. n_runs - 1 to the
+//                        runs, newest first, and takes TwoMergeIterator's eager step (the SST
+//                        cursors leave a key a run holds before that key is looked at), and the
+//                        gather reads run entries too.
 //
 // No kernel needs a workgroup barrier. The gather trusts nothing it is handed: table, block and
 // entry are checked against the descriptors, counts are clamped to `limit` and to d_first's total,
@@ -33,6 +42,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "tpz_copy.h"
 #include "tpz_internal.h"
@@ -49,7 +60,8 @@ using scandev::SeekParams;
 using seekdev::u32;
 using seekdev::u64;
 
-// The bodies are tpz_scan_dev.h's, without the memtable side (tpz_mem.hip runs them with it).
+// The bodies are tpz_scan_dev.h's, without the memtable side (the lsm_scan_* kernels below run
+// them with it).
 __global__ __launch_bounds__(256) void scan_seek_kernel(SeekParams p) {
   scandev::seek_body<false>(p, scandev::Runs{nullptr, 0});
 }
@@ -72,11 +84,36 @@ __global__ __launch_bounds__(256) void scan_entries_kernel(EntriesParams p) {
   scandev::entries_body<kCopy, false>(p, scandev::Runs{nullptr, 0});
 }
 
+// LsmStorage::scan whole: the same bodies with the memtable side.
+struct LsmSeekParams {
+  scandev::SeekParams s;
+  scandev::Runs m;
+};
+__global__ __launch_bounds__(256) void lsm_scan_seek_kernel(LsmSeekParams p) {
+  scandev::seek_body<true>(p.s, p.m);
+}
+
+struct LsmMergeParams {
+  scandev::MergeParams s;
+  scandev::Runs m;
+};
+__global__ __launch_bounds__(256) void lsm_scan_merge_kernel(LsmMergeParams p) {
+  scandev::merge_body<true>(p.s, p.m);
+}
+
+struct LsmEntriesParams {
+  scandev::EntriesParams s;
+  scandev::Runs m;
+};
+template <bool kCopy>
+__global__ __launch_bounds__(256) void lsm_scan_entries_kernel(LsmEntriesParams p) {
+  scandev::entries_body<kCopy, true>(p.s, p.m);
+}
+
 }  // namespace
 
-uint64_t scan_ranges_work_bytes(uint32_t n_scans, uint32_t n_tables) {
-  const uint64_t cells = (uint64_t)n_scans * n_tables;
-  return 8 * cells + ((cells + 7) & ~7ull) + 8 * (flat_scan_parts_words(n_scans) / 3);
+uint64_t scan_ranges_work_bytes(uint32_t n_scans, uint32_t n_cursors) {
+  return scandev::cursor_work_bytes(n_scans, (uint64_t)n_scans * n_cursors, 2);
 }
 
 uint64_t scan_entries_work_bytes(uint32_t n_scans) {
@@ -92,34 +129,47 @@ void launch_scan_totals(const ScanLaunch& a, uint64_t* part, hipStream_t stream)
 }
 
 void launch_scan_ranges(const ScanLaunch& a, hipStream_t stream) {
-  const uint64_t cells = (uint64_t)a.n_scans * a.n_tables;
-  u32* cur = static_cast<u32*>(a.work);
-  uint8_t* cst = reinterpret_cast<uint8_t*>(cur + 2 * cells);
-  u64* part = reinterpret_cast<u64*>(cst + ((cells + 7) & ~7ull));
-  if (cells) {
-    SeekParams s{a.tabs, a.n_tables, a.l0, a.lo, a.lo_pos, a.lo_kind, a.hi, a.hi_pos, a.hi_kind,
-                 a.n_scans, cur, cst};
-    hipLaunchKernelGGL(scan_seek_kernel, dim3((u32)((cells + 255) / 256)), dim3(256), 0, stream, s);
+  if (a.flavour == Flavour::kLevel) return launch_level_scan_ranges(a, stream);
+  const bool mem = a.flavour == Flavour::kLsm;
+  const uint64_t cells = (uint64_t)a.n_scans * (a.n_tables + (mem ? a.n_runs : 0u));
+  const scandev::CursorWork w = scandev::carve_cursors(a.work, cells, 2);
+  const SeekParams sp = scandev::seek_params(a, w);
+  const MergeParams mp = scandev::merge_params(a, w);
+  const scandev::Runs m{a.runs, a.n_runs};
+  const dim3 seek_grid((u32)((cells + 255) / 256)), merge_grid((a.n_scans + kWaves - 1) / kWaves);
+  if (mem) {
+    const LsmSeekParams ls{sp, m};
+    const LsmMergeParams lm{mp, m};
+    if (cells) hipLaunchKernelGGL(lsm_scan_seek_kernel, seek_grid, dim3(256), 0, stream, ls);
+    hipLaunchKernelGGL(lsm_scan_merge_kernel, merge_grid, dim3(256), 0, stream, lm);
+  } else {
+    if (cells) hipLaunchKernelGGL(scan_seek_kernel, seek_grid, dim3(256), 0, stream, sp);
+    hipLaunchKernelGGL(scan_merge_kernel, merge_grid, dim3(256), 0, stream, mp);
   }
-  MergeParams m{a.tabs, a.n_tables, a.l0, a.hi, a.hi_pos, a.lo_kind, a.hi_kind, a.n_scans, a.limit,
-                cur, cst, a.result, a.status, a.where, a.hit_table, a.hit_block, a.hit_entry,
-                a.first, a.key_first, a.val_first};
-  hipLaunchKernelGGL(scan_merge_kernel, dim3((a.n_scans + kWaves - 1) / kWaves), dim3(256), 0,
-                     stream, m);
-  launch_scan_totals(a, part, stream);
+  launch_scan_totals(a, w.part, stream);
 }
 
 void launch_scan_entries(const ScanEntriesLaunch& a, hipStream_t stream) {
   u64* kbase = static_cast<u64*>(a.work);
   u64* vbase = kbase + a.n_scans + 1;
   u64* part = vbase + a.n_scans + 1;
-  EntriesParams p{a.tabs, a.n_tables, a.n_scans, a.limit, a.hit_table, a.hit_block, a.hit_entry,
-                  a.first, kbase, vbase, a.keys, a.key_cap, a.kpos, a.vals, a.val_cap, a.vpos};
+  const EntriesParams p{a.tabs, a.n_tables, a.n_scans, a.limit, a.hit_table, a.hit_block,
+                        a.hit_entry, a.first, kbase, vbase, a.keys, a.key_cap, a.kpos, a.vals,
+                        a.val_cap, a.vpos};
+  const LsmEntriesParams lp{p, {a.runs, a.n_runs}};
+  const bool mem = a.flavour != Flavour::kTables;   // kLsm and kLevel: hits in runs too
   const dim3 grid((a.n_scans + kWaves - 1) / kWaves);
-  hipLaunchKernelGGL(scan_entries_kernel<false>, grid, dim3(256), 0, stream, p);
+  auto pass = [&](auto copy) {
+    constexpr bool kCopy = decltype(copy)::value;
+    if (mem)
+      hipLaunchKernelGGL(lsm_scan_entries_kernel<kCopy>, grid, dim3(256), 0, stream, lp);
+    else
+      hipLaunchKernelGGL(scan_entries_kernel<kCopy>, grid, dim3(256), 0, stream, p);
+  };
+  pass(std::false_type{});                          // the lengths
   launch_scan_u64(kbase, a.n_scans, part, stream);
   launch_scan_u64(vbase, a.n_scans, part, stream);
-  hipLaunchKernelGGL(scan_entries_kernel<true>, grid, dim3(256), 0, stream, p);
+  pass(std::true_type{});                           // the positions and the copies
 }
 
 }  // namespace tpz

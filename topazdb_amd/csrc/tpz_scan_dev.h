@@ -1,5 +1,5 @@
-// tpz_scan_dev.h — the bodies of the scan's kernels, shared by tpz_scan.hip (tpz_scan_ranges,
-// tpz_scan_entries: the SST half of LsmStorage::scan) and tpz_mem.hip (tpz_lsm_scan_ranges,
+// tpz_scan_dev.h — the bodies of the scan's kernels, shared by tpz_scan.hip's two sets of them
+// (tpz_scan_ranges, tpz_scan_entries: the SST half of LsmStorage::scan; tpz_lsm_scan_ranges,
 // tpz_lsm_scan_entries: the whole scan, memtable runs merged in). kMem = false is the SST half as
 // it always was; kMem = true puts one cursor per run in front of the tables' (a wave's lanes
 // 0 .. n_runs - 1, the newest run first) and adds TwoMergeIterator's eager step to the merge.
@@ -614,6 +614,32 @@ __device__ __forceinline__ void entries_body(const EntriesParams& p, const Runs&
       p.vpos[total] = vb;
     }
   }
+}
+
+// Host side, for the launchers of tpz_scan.hip and tpz_levelscan.hip: the cursors' part of a
+// ranges call's workspace (`words` u32 per scan and cursor: 2, or kLvl's 4; then a status byte
+// each, padded to 8; then the scans' partial sums) and the kernels' parameters from a ScanLaunch.
+struct CursorWork {
+  u32* cur;
+  uint8_t* cst;
+  u64* part;
+};
+inline uint64_t cursor_work_bytes(uint32_t n_scans, uint64_t cells, u32 words) {
+  return 4 * words * cells + ((cells + 7) & ~7ull) + 8 * (flat_scan_parts_words(n_scans) / 3);
+}
+inline CursorWork carve_cursors(void* work, uint64_t cells, u32 words) {
+  u32* cur = static_cast<u32*>(work);
+  uint8_t* cst = reinterpret_cast<uint8_t*>(cur + words * cells);
+  return {cur, cst, reinterpret_cast<u64*>(cst + ((cells + 7) & ~7ull))};
+}
+inline SeekParams seek_params(const ScanLaunch& a, const CursorWork& w) {
+  return {a.tabs, a.n_tables, a.l0(), a.lo, a.lo_pos, a.lo_kind, a.hi, a.hi_pos, a.hi_kind,
+          a.n_scans, w.cur, w.cst};
+}
+inline MergeParams merge_params(const ScanLaunch& a, const CursorWork& w) {
+  return {a.tabs, a.n_tables, a.l0(), a.hi, a.hi_pos, a.lo_kind, a.hi_kind, a.n_scans, a.limit,
+          w.cur, w.cst, a.result, a.status, a.where, a.hit_table, a.hit_block, a.hit_entry,
+          a.first, a.key_first, a.val_first};
 }
 
 }  // namespace scandev

@@ -136,9 +136,28 @@ class DeviceLevels:
         raw = np.frombuffer(bytes(desc), np.uint8).copy()
         self.d_tables = torch.from_numpy(raw).to(self.dev)       # uploaded once
 
+    # What DeviceLsm adds: the ABI family of its calls, and its memtable runs.
+    _family = ""                # tpz_get_* / tpz_scan_*
+    n_runs = 0
+
+    def _runs(self) -> tuple:
+        """(d_runs pointer, n_runs) for the calls that take memtable runs."""
+        return 0, 0
+
+    def _call(self, op: str, by_level: bool, *args) -> None:
+        """tpz_<family><op> over the tables (the lsm family: the runs in front), or with
+        by_level (scans only) tpz_level_<op> over the runs and the tables."""
+        if by_level:
+            getattr(self.ctx, f"level_{op}_ptrs")(*self._runs(), *args)
+        elif self._family:
+            getattr(self.ctx, f"{self._family}{op}_ptrs")(*self._runs(), *args)
+        else:
+            getattr(self.ctx, f"{op}_ptrs")(*args)
+
     def walk(self, keys: list[bytes]) -> dict:
-        """tpz_get_keys on the current stream: device tensors result, status (uint8), table,
-        block, entry (int32 holding the u32 values), val_pos (int64, n + 1), and n."""
+        """tpz_get_keys (DeviceLsm: tpz_lsm_get_keys) on the current stream: device tensors
+        result, status (uint8), table, block, entry (int32 holding the u32 values), val_pos
+        (int64, n + 1), and n."""
         n = len(keys)
         buf, pos = _pack(keys)
         q = torch.from_numpy(buf.copy()).to(self.dev)
@@ -147,25 +166,23 @@ class DeviceLevels:
                (("result", torch.uint8), ("status", torch.uint8), ("table", torch.int32),
                 ("block", torch.int32), ("entry", torch.int32))}
         out["val_pos"] = torch.empty(n + 1, dtype=torch.int64, device=self.dev)
-        self.ctx.get_keys_ptrs(self.d_tables.data_ptr(), self.n_tables,
-                               self.level_first.ctypes.data, self.n_levels, q.data_ptr(),
-                               qp.data_ptr(), n, out["result"].data_ptr(),
-                               out["status"].data_ptr(), out["table"].data_ptr(),
-                               out["block"].data_ptr(), out["entry"].data_ptr(),
-                               out["val_pos"].data_ptr(),
-                               torch.cuda.current_stream(self.dev).cuda_stream)
+        self._call("get_keys", False, self.d_tables.data_ptr(), self.n_tables,
+                   self.level_first.ctypes.data, self.n_levels, q.data_ptr(), qp.data_ptr(), n,
+                   out["result"].data_ptr(), out["status"].data_ptr(), out["table"].data_ptr(),
+                   out["block"].data_ptr(), out["entry"].data_ptr(), out["val_pos"].data_ptr(),
+                   torch.cuda.current_stream(self.dev).cuda_stream)
         out["n"] = n
         out["_keys"] = (q, qp)      # alive until the stream has run the walk
         return out
 
     def values(self, w: dict, total: int) -> torch.Tensor:
-        """tpz_get_values on the current stream: the packed values (uint8, `total` bytes)."""
+        """tpz_get_values (DeviceLsm: tpz_lsm_get_values) on the current stream: the packed
+        values (uint8, `total` bytes)."""
         vals = torch.empty(max(total, 1), dtype=torch.uint8, device=self.dev)
-        self.ctx.get_values_ptrs(self.d_tables.data_ptr(), self.n_tables, w["n"],
-                                 w["result"].data_ptr(), w["table"].data_ptr(),
-                                 w["block"].data_ptr(), w["entry"].data_ptr(),
-                                 w["val_pos"].data_ptr(), vals.data_ptr(), total,
-                                 torch.cuda.current_stream(self.dev).cuda_stream)
+        self._call("get_values", False, self.d_tables.data_ptr(), self.n_tables, w["n"],
+                   w["result"].data_ptr(), w["table"].data_ptr(), w["block"].data_ptr(),
+                   w["entry"].data_ptr(), w["val_pos"].data_ptr(), vals.data_ptr(), total,
+                   torch.cuda.current_stream(self.dev).cuda_stream)
         return vals[:total]
 
     def get_batch(self, keys: list[bytes]) -> dict:
@@ -185,11 +202,12 @@ class DeviceLevels:
         return out
 
     def scan_ranges(self, ranges: list, limit: int, by_level: bool = False) -> dict:
-        """tpz_scan_ranges on the current stream: device tensors result, status (uint8), where
-        (int32, n x 3), hit_table, hit_block, hit_entry (int32, n x limit), first, key_first,
-        val_first (int64, n + 1), info (int64, 3), and n, limit. More than SCAN_MAX_TABLES tables,
-        or by_level: tpz_level_scan_ranges (one cursor per level below L0)."""
-        by_level = by_level or self.n_tables > _lib.SCAN_MAX_TABLES
+        """tpz_scan_ranges (DeviceLsm: tpz_lsm_scan_ranges) on the current stream: device tensors
+        result, status (uint8), where (int32, n x 3), hit_table, hit_block, hit_entry (int32,
+        n x limit), first, key_first, val_first (int64, n + 1), info (int64, 3), and n, limit.
+        More than SCAN_MAX_TABLES runs plus tables, or by_level: tpz_level_scan_ranges (one cursor
+        per level below L0)."""
+        by_level = by_level or self.n_runs + self.n_tables > _lib.SCAN_MAX_TABLES
         n = len(ranges)
         lo = [_bound(r[0], True) for r in ranges]
         hi = [_bound(r[1], False) for r in ranges]
@@ -206,38 +224,33 @@ class DeviceLevels:
         for k in ("first", "key_first", "val_first"):
             out[k] = torch.empty(n + 1, dtype=torch.int64, device=dev)
         out["info"] = torch.empty(3, dtype=torch.int64, device=dev)
-        args = (self.d_tables.data_ptr(), self.n_tables, self.level_first.ctypes.data,
-                self.n_levels, *(c.data_ptr() for c in cols), n, limit,
-                *(out[k].data_ptr() for k in
-                  ("result", "status", "where", "hit_table", "hit_block", "hit_entry", "first",
-                   "key_first", "val_first", "info")),
-                torch.cuda.current_stream(dev).cuda_stream)
-        if by_level:
-            self.ctx.level_scan_ranges_ptrs(0, 0, *args)
-        else:
-            self.ctx.scan_ranges_ptrs(*args)
+        self._call("scan_ranges", by_level, self.d_tables.data_ptr(), self.n_tables,
+                   self.level_first.ctypes.data, self.n_levels, *(c.data_ptr() for c in cols), n,
+                   limit,
+                   *(out[k].data_ptr() for k in
+                     ("result", "status", "where", "hit_table", "hit_block", "hit_entry", "first",
+                      "key_first", "val_first", "info")),
+                   torch.cuda.current_stream(dev).cuda_stream)
         out["n"], out["limit"], out["by_level"] = n, limit, by_level
         out["_bounds"] = cols        # alive until the stream has run the scan
         return out
 
     def scan_entries(self, s: dict, totals) -> dict:
-        """tpz_scan_entries on the current stream over scan_ranges' outputs: device tensors kpos,
-        vpos (int64, entries + 1), keys, values (uint8). totals = the three numbers of info."""
+        """tpz_scan_entries (DeviceLsm: tpz_lsm_scan_entries; by_level: tpz_level_scan_entries) on
+        the current stream over scan_ranges' outputs: device tensors kpos, vpos (int64, entries +
+        1), keys, values (uint8). totals = the three numbers of info."""
         n_ent, kbytes, vbytes = (int(x) for x in totals)
         dev = self.dev
         out = {"kpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
                "vpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
                "keys": torch.empty(max(kbytes, 1), dtype=torch.uint8, device=dev),
                "values": torch.empty(max(vbytes, 1), dtype=torch.uint8, device=dev)}
-        args = (self.d_tables.data_ptr(), self.n_tables, s["n"], s["limit"],
-                s["hit_table"].data_ptr(), s["hit_block"].data_ptr(), s["hit_entry"].data_ptr(),
-                s["first"].data_ptr(), out["keys"].data_ptr(), kbytes, out["kpos"].data_ptr(),
-                out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
-                torch.cuda.current_stream(dev).cuda_stream)
-        if s.get("by_level"):
-            self.ctx.level_scan_entries_ptrs(0, 0, *args)
-        else:
-            self.ctx.scan_entries_ptrs(*args)
+        self._call("scan_entries", bool(s.get("by_level")), self.d_tables.data_ptr(),
+                   self.n_tables, s["n"], s["limit"], s["hit_table"].data_ptr(),
+                   s["hit_block"].data_ptr(), s["hit_entry"].data_ptr(), s["first"].data_ptr(),
+                   out["keys"].data_ptr(), kbytes, out["kpos"].data_ptr(),
+                   out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
+                   torch.cuda.current_stream(dev).cuda_stream)
         out["keys"], out["values"] = out["keys"][:kbytes], out["values"][:vbytes]
         return out
 
@@ -375,86 +388,10 @@ class DeviceLsm(DeviceLevels):
         raw = np.frombuffer(bytes(desc), np.uint8).copy()
         self.d_runs = torch.from_numpy(raw).to(self.dev)         # uploaded once
 
-    def walk(self, keys: list[bytes]) -> dict:
-        """tpz_lsm_get_keys on the current stream: DeviceLevels.walk's outputs."""
-        n = len(keys)
-        buf, pos = _pack(keys)
-        q = torch.from_numpy(buf.copy()).to(self.dev)
-        qp = torch.from_numpy(pos).to(self.dev)
-        out = {k: torch.empty(max(n, 1), dtype=t, device=self.dev) for k, t in
-               (("result", torch.uint8), ("status", torch.uint8), ("table", torch.int32),
-                ("block", torch.int32), ("entry", torch.int32))}
-        out["val_pos"] = torch.empty(n + 1, dtype=torch.int64, device=self.dev)
-        self.ctx.lsm_get_keys_ptrs(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(),
-                                   self.n_tables, self.level_first.ctypes.data, self.n_levels,
-                                   q.data_ptr(), qp.data_ptr(), n, out["result"].data_ptr(),
-                                   out["status"].data_ptr(), out["table"].data_ptr(),
-                                   out["block"].data_ptr(), out["entry"].data_ptr(),
-                                   out["val_pos"].data_ptr(),
-                                   torch.cuda.current_stream(self.dev).cuda_stream)
-        out["n"] = n
-        out["_keys"] = (q, qp)      # alive until the stream has run the walk
-        return out
+    _family = "lsm_"            # tpz_lsm_get_* / tpz_lsm_scan_*
 
-    def values(self, w: dict, total: int) -> torch.Tensor:
-        """tpz_lsm_get_values on the current stream: the packed values (uint8, `total` bytes)."""
-        vals = torch.empty(max(total, 1), dtype=torch.uint8, device=self.dev)
-        self.ctx.lsm_get_values_ptrs(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(),
-                                     self.n_tables, w["n"], w["result"].data_ptr(),
-                                     w["table"].data_ptr(), w["block"].data_ptr(),
-                                     w["entry"].data_ptr(), w["val_pos"].data_ptr(),
-                                     vals.data_ptr(), total,
-                                     torch.cuda.current_stream(self.dev).cuda_stream)
-        return vals[:total]
-
-    def scan_ranges(self, ranges: list, limit: int, by_level: bool = False) -> dict:
-        """tpz_lsm_scan_ranges on the current stream: DeviceLevels.scan_ranges' outputs. More than
-        SCAN_MAX_TABLES runs plus tables, or by_level: tpz_level_scan_ranges."""
-        by_level = by_level or self.n_runs + self.n_tables > _lib.SCAN_MAX_TABLES
-        n = len(ranges)
-        lo = [_bound(r[0], True) for r in ranges]
-        hi = [_bound(r[1], False) for r in ranges]
-        dev = self.dev
-        cols = []
-        for side in (lo, hi):
-            buf, pos = _pack([k for _, k in side])
-            cols += [torch.from_numpy(buf.copy()).to(dev), torch.from_numpy(pos).to(dev),
-                     torch.from_numpy(np.array([k for k, _ in side] or [0], np.uint8)).to(dev)]
-        out = {k: torch.empty(max(n, 1), dtype=torch.uint8, device=dev) for k in ("result", "status")}
-        out["where"] = torch.empty((max(n, 1), 3), dtype=torch.int32, device=dev)
-        for k in ("hit_table", "hit_block", "hit_entry"):
-            out[k] = torch.empty(max(n * limit, 1), dtype=torch.int32, device=dev)
-        for k in ("first", "key_first", "val_first"):
-            out[k] = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        out["info"] = torch.empty(3, dtype=torch.int64, device=dev)
-        call = self.ctx.level_scan_ranges_ptrs if by_level else self.ctx.lsm_scan_ranges_ptrs
-        call(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(), self.n_tables,
-             self.level_first.ctypes.data, self.n_levels, *(c.data_ptr() for c in cols), n, limit,
-             *(out[k].data_ptr() for k in
-               ("result", "status", "where", "hit_table", "hit_block", "hit_entry", "first",
-                "key_first", "val_first", "info")),
-             torch.cuda.current_stream(dev).cuda_stream)
-        out["n"], out["limit"], out["by_level"] = n, limit, by_level
-        out["_bounds"] = cols        # alive until the stream has run the scan
-        return out
-
-    def scan_entries(self, s: dict, totals) -> dict:
-        """tpz_lsm_scan_entries on the current stream over scan_ranges' outputs."""
-        n_ent, kbytes, vbytes = (int(x) for x in totals)
-        dev = self.dev
-        out = {"kpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
-               "vpos": torch.empty(n_ent + 1, dtype=torch.int64, device=dev),
-               "keys": torch.empty(max(kbytes, 1), dtype=torch.uint8, device=dev),
-               "values": torch.empty(max(vbytes, 1), dtype=torch.uint8, device=dev)}
-        call = (self.ctx.level_scan_entries_ptrs if s.get("by_level")
-                else self.ctx.lsm_scan_entries_ptrs)
-        call(self.d_runs.data_ptr(), self.n_runs, self.d_tables.data_ptr(), self.n_tables, s["n"],
-             s["limit"], s["hit_table"].data_ptr(), s["hit_block"].data_ptr(),
-             s["hit_entry"].data_ptr(), s["first"].data_ptr(), out["keys"].data_ptr(), kbytes,
-             out["kpos"].data_ptr(), out["values"].data_ptr(), vbytes, out["vpos"].data_ptr(),
-             torch.cuda.current_stream(dev).cuda_stream)
-        out["keys"], out["values"] = out["keys"][:kbytes], out["values"][:vbytes]
-        return out
+    def _runs(self) -> tuple:
+        return self.d_runs.data_ptr(), self.n_runs
 
     def scan(self, lower=None, upper=None, page: int = 256) -> ScanIterator:
         """lsm_storage.rs:335-374: is_valid() / key() / value() / next(). A page that reported
