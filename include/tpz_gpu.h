@@ -1394,6 +1394,87 @@ tpz_err tpz_table_runs_entries(tpz_ctx* ctx, const tpz_table* d_tables, uint32_t
                                uint8_t* d_vals, uint64_t val_cap, uint64_t* d_vpos,
                                uint64_t entry_cap, void* stream);
 
+/* ---- point gets from encoded blocks in place ---------------------------------------------
+ * An in-place table is a resident table without decoded columns: its blocks are read where they
+ * lie, in the Uncompress form payload | crc u32 BE | tag 1 with payload = n u16 BE | n offsets
+ * u16 BE | data (src/block.rs:31-44, src/block/compress.rs:85-89); blocks stored with a codec
+ * take tpz_decompress_blocks first, whose output is that form. The device does on those bytes
+ * what BlockIterator does (src/block/iterator.rs:63-109): seek_to_key bisects over offsets[mid],
+ * reads klen and compares the key (:91-109); seek_to reads vlen and the value (:74-82). A served
+ * table then costs its encoded bytes plus 17 bytes per block (d_ext, d_first_pos, d_status) and
+ * its first keys, not the decoded columns on top. Additive within ABI 8: new symbols only
+ * (TPZ_HAS_RAW_TABLES tells a consumer the header has them). Scans, level scans and compaction
+ * inputs still take decoded tables (tpz_table).
+ *
+ * tpz_raw_verify: what Block::decode does before any entry is read (src/block.rs:46-59,
+ * src/block/compress.rs:95-113), for every block of `batch`: the tag dispatch, the CRC over the
+ * payload, n and the n offsets readable.
+ *   d_status[b]  what tpz_decode_blocks reports for the same batch, except that
+ *                TPZ_BLOCK_OK_SPILLED and TPZ_BLOCK_BAD_ENTRY read as TPZ_BLOCK_OK (no entry is
+ *                read: a bad entry fails lazily, where a seek touches it, as in the reference)
+ *   d_crc[b]     the CRC-32 computed over the payload, as tpz_decode_blocks' d_crc (0 for EMPTY,
+ *                BAD_TAG, UNSUPPORTED_CODEC and a block shorter than 5 bytes)
+ * Device memory: the caller's two columns and n_blocks u32 of the stream's workspace; nothing
+ * proportional to the data bytes. batch->d_src may have any alignment. n_blocks == 0 is valid.
+ *
+ * tpz_raw_table: d_first_keys / d_first_pos as tpz_table; block b is d_src[d_ext[b] ..
+ * d_ext[b + 1]) (any byte offset; extents may pass 2^32); d_status = tpz_raw_verify's column;
+ * d_filter as tpz_get_table's. An entry is named (block, entry index) as in a decoded table.
+ *
+ * tpz_raw_seek_keys = tpz_seek_keys, tpz_raw_get_keys / tpz_raw_get_values = tpz_get_keys /
+ * tpz_get_values, tpz_raw_lsm_get_keys / tpz_raw_lsm_get_values = tpz_lsm_get_keys /
+ * tpz_lsm_get_values (memtable runs in front, the TPZ_HIT_MEM convention), each over in-place
+ * tables: the same outputs, statuses, panics classes, preconditions and TPZ_ERR_INVALID_ARG rules
+ * (n_levels > TPZ_GET_MAX_LEVELS, a bad h_level_first, n_runs > TPZ_MEM_MAX_RUNS, null or
+ * misaligned pointers; n_keys == 0 and n_tables == 0 are valid). An entry whose key read panics
+ * in the reference (offset past the data, klen unreadable or past the end: :97-100) gives
+ * TPZ_BLOCK_MALFORMED where the bisection reads it, one whose value read panics (:80-82) where
+ * the seek lands on it; entries the seek does not touch do not matter. With descriptors or block
+ * bytes that changed after tpz_raw_verify the results are unspecified, but every loop is bounded
+ * and no byte outside a block's extent is read. */
+#define TPZ_HAS_RAW_TABLES 1
+/* (declared with a tag, as tpz_get_table is) */
+struct tpz_raw_table {
+  const uint8_t* d_first_keys; /* as tpz_table */
+  const uint64_t* d_first_pos; /* n_blocks + 1 */
+  const uint8_t* d_src;        /* the blocks where they lie (Uncompress form, tag 1) */
+  const uint64_t* d_ext;       /* n_blocks + 1 extents into d_src */
+  uint32_t n_blocks;
+  const uint8_t* d_status;     /* tpz_raw_verify's, one byte per block */
+  const uint8_t* d_filter;     /* Bloom::encode or NULL */
+  uint64_t filter_len;
+};
+typedef struct tpz_raw_table tpz_raw_table;
+
+tpz_err tpz_raw_verify(tpz_ctx* ctx, const tpz_batch* batch, uint8_t* d_status, uint32_t* d_crc,
+                       void* stream);
+tpz_err tpz_raw_seek_keys(tpz_ctx* ctx, const tpz_raw_table* table, const uint8_t* d_keys,
+                          const uint64_t* d_key_pos, uint32_t n_keys, uint32_t* d_block,
+                          uint32_t* d_entry, uint8_t* d_status, uint8_t* d_valid, void* stream);
+tpz_err tpz_raw_get_keys(tpz_ctx* ctx, const tpz_raw_table* d_tables, uint32_t n_tables,
+                         const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                         const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                         uint8_t* d_status, uint32_t* d_table, uint32_t* d_block,
+                         uint32_t* d_entry, uint64_t* d_val_pos, void* stream);
+tpz_err tpz_raw_get_values(tpz_ctx* ctx, const tpz_raw_table* d_tables, uint32_t n_tables,
+                           uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
+                           const uint32_t* d_block, const uint32_t* d_entry,
+                           const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
+                           void* stream);
+tpz_err tpz_raw_lsm_get_keys(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                             const tpz_raw_table* d_tables, uint32_t n_tables,
+                             const uint32_t* h_level_first, uint32_t n_levels,
+                             const uint8_t* d_keys, const uint64_t* d_key_pos, uint32_t n_keys,
+                             uint8_t* d_result, uint8_t* d_status, uint32_t* d_table,
+                             uint32_t* d_block, uint32_t* d_entry, uint64_t* d_val_pos,
+                             void* stream);
+tpz_err tpz_raw_lsm_get_values(tpz_ctx* ctx, const tpz_mem_run* d_runs, uint32_t n_runs,
+                               const tpz_raw_table* d_tables, uint32_t n_tables, uint32_t n_keys,
+                               const uint8_t* d_result, const uint32_t* d_table,
+                               const uint32_t* d_block, const uint32_t* d_entry,
+                               const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
+                               void* stream);
+
 /* ---- host write side (inputs for benches and the table facade) ---------------------------
  * SsTableBuilder::add + block_build (src/table/builder.rs:49-85) with BlockBuilder's fill rule
  * (src/block/builder.rs:26-41) and Block::encode + Uncompress (src/block.rs:31-44,

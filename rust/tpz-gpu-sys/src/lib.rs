@@ -116,6 +116,10 @@ pub const TPZ_OPEN_UNSUPPORTED: u64 = 7;
 /// resident tables gathered into the runs `tpz_merge_runs` takes.
 pub const TPZ_HAS_TABLE_RUNS: u32 = 1;
 
+/// The header declares `tpz_raw_verify` and the `tpz_raw_*` seek and get calls (additive within
+/// ABI 8): point gets served from the encoded blocks in place, without decoded columns.
+pub const TPZ_HAS_RAW_TABLES: u32 = 1;
+
 /// `tpz_open_scratch_bytes` (a static inline of the header): 16 bytes per tile of the span plus
 /// two tiles per file.
 pub const fn tpz_open_scratch_bytes(span_bytes: u64, n_files: u64) -> u64 {
@@ -216,6 +220,25 @@ pub struct TpzGetTable {
 /// The header declares this struct with a tag, so the extern block names it as the header does.
 #[allow(non_camel_case_types)]
 pub type tpz_get_table = TpzGetTable;
+
+/// `tpz_raw_table`: an in-place table: its encoded blocks where they lie in HBM (Uncompress form),
+/// `tpz_raw_verify`'s status column, its block first keys and its bloom filter (`d_filter` null:
+/// no filter).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct TpzRawTable {
+    pub d_first_keys: *const u8,
+    pub d_first_pos: *const u64,
+    pub d_src: *const u8,
+    pub d_ext: *const u64,
+    pub n_blocks: u32,
+    pub d_status: *const u8,
+    pub d_filter: *const u8,
+    pub filter_len: u64,
+}
+/// Declared with a tag in the header, as `tpz_get_table` is.
+#[allow(non_camel_case_types)]
+pub type tpz_raw_table = TpzRawTable;
 
 /// `tpz_sst_image`: one output table of `tpz_sst_finish`; its data region sits at `d_image`
 /// already (`d_filter` null: no bloom section).
@@ -460,6 +483,34 @@ extern "C" {
                                   d_keys: *mut u8, key_cap: u64, d_kpos: *mut u64,
                                   d_vals: *mut u8, val_cap: u64, d_vpos: *mut u64,
                                   entry_cap: u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_raw_verify(ctx: *mut TpzCtx, batch: *const TpzBatch, d_status: *mut u8,
+                          d_crc: *mut u32, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_raw_seek_keys(ctx: *mut TpzCtx, table: *const tpz_raw_table, d_keys: *const u8,
+                             d_key_pos: *const u64, n_keys: u32, d_block: *mut u32,
+                             d_entry: *mut u32, d_status: *mut u8, d_valid: *mut u8,
+                             stream: *mut c_void) -> TpzErr;
+    pub fn tpz_raw_get_keys(ctx: *mut TpzCtx, d_tables: *const tpz_raw_table, n_tables: u32,
+                            h_level_first: *const u32, n_levels: u32, d_keys: *const u8,
+                            d_key_pos: *const u64, n_keys: u32, d_result: *mut u8,
+                            d_status: *mut u8, d_table: *mut u32, d_block: *mut u32,
+                            d_entry: *mut u32, d_val_pos: *mut u64,
+                            stream: *mut c_void) -> TpzErr;
+    pub fn tpz_raw_get_values(ctx: *mut TpzCtx, d_tables: *const tpz_raw_table, n_tables: u32,
+                              n_keys: u32, d_result: *const u8, d_table: *const u32,
+                              d_block: *const u32, d_entry: *const u32, d_val_pos: *const u64,
+                              d_vals: *mut u8, val_cap: u64, stream: *mut c_void) -> TpzErr;
+    pub fn tpz_raw_lsm_get_keys(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                                d_tables: *const tpz_raw_table, n_tables: u32,
+                                h_level_first: *const u32, n_levels: u32, d_keys: *const u8,
+                                d_key_pos: *const u64, n_keys: u32, d_result: *mut u8,
+                                d_status: *mut u8, d_table: *mut u32, d_block: *mut u32,
+                                d_entry: *mut u32, d_val_pos: *mut u64,
+                                stream: *mut c_void) -> TpzErr;
+    pub fn tpz_raw_lsm_get_values(ctx: *mut TpzCtx, d_runs: *const tpz_mem_run, n_runs: u32,
+                                  d_tables: *const tpz_raw_table, n_tables: u32, n_keys: u32,
+                                  d_result: *const u8, d_table: *const u32, d_block: *const u32,
+                                  d_entry: *const u32, d_val_pos: *const u64, d_vals: *mut u8,
+                                  val_cap: u64, stream: *mut c_void) -> TpzErr;
     pub fn tpz_build_blocks(h_keys: *const u8, h_kpos: *const u64, h_vals: *const u8,
                             h_vpos: *const u64, n_entries: u64, block_size: u32, h_out: *mut u8,
                             out_cap: u64, h_ext: *mut u64, ext_cap: u64, n_blocks: *mut u64,

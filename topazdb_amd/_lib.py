@@ -46,6 +46,7 @@ OPEN_TILE = 4096          # TPZ_OPEN_TILE: bytes of meta section per checkpoint 
 # tpz_open_index's d_info[8f] (TPZ_OPEN_*)
 (OPEN_OK, OPEN_SHORT, OPEN_BLOOM_RANGE, OPEN_META_RANGE, OPEN_META_TRUNCATED, OPEN_BAD_EXTENTS,
  OPEN_NO_BLOCKS, OPEN_UNSUPPORTED) = range(8)
+HAS_RAW_TABLES = 1        # TPZ_HAS_RAW_TABLES: the tpz_raw_* calls over in-place tables
 LDS_BLOCK_BYTES = 94192  # TPZ_LDS_BLOCK_BYTES: longer blocks with 64+ entries take the spill path
 BIGWAVE_BLOCK_BYTES = 0x40000000   # TPZ_BIGWAVE_BLOCK_BYTES
 
@@ -92,6 +93,14 @@ class GetTable(C.Structure):
     """tpz_get_table: a resident table of tpz_get_keys (its tpz_table plus its bloom filter;
     d_filter None: no filter)."""
     _fields_ = [("table", Table), ("d_filter", C.c_void_p), ("filter_len", C.c_uint64)]
+
+
+class RawTable(C.Structure):
+    """tpz_raw_table: an in-place table (its encoded blocks where they lie, tpz_raw_verify's
+    status column, its block first keys and its bloom filter; d_filter None: no filter)."""
+    _fields_ = [("d_first_keys", C.c_void_p), ("d_first_pos", C.c_void_p), ("d_src", C.c_void_p),
+                ("d_ext", C.c_void_p), ("n_blocks", C.c_uint32), ("d_status", C.c_void_p),
+                ("d_filter", C.c_void_p), ("filter_len", C.c_uint64)]
 
 
 class Entries(C.Structure):
@@ -321,6 +330,18 @@ def lib() -> C.CDLL:
                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                              C.c_void_p]
         L.tpz_table_runs_entries.restype = C.c_int
+        if not hasattr(L, "tpz_raw_verify"):      # (additive within ABI 8: an older build lacks it)
+            raise TpzError(f"{LIB_PATH} does not export tpz_raw_verify: rebuild (make -C "
+                           "topazdb_amd/csrc)")
+        L.tpz_raw_verify.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+        L.tpz_raw_verify.restype = C.c_int
+        L.tpz_raw_seek_keys.argtypes = [C.c_void_p, C.POINTER(RawTable)] + \
+            list(L.tpz_seek_keys.argtypes[2:])
+        L.tpz_raw_seek_keys.restype = C.c_int
+        for f in ("get_keys", "get_values", "lsm_get_keys", "lsm_get_values"):
+            getattr(L, "tpz_raw_" + f).argtypes = list(getattr(L, "tpz_" + f).argtypes)
+            getattr(L, "tpz_raw_" + f).restype = C.c_int
         if hasattr(L, "tpz_debug_table_runs_entries"):   # diagnostic (not in tpz_gpu.h): runs_probe.py
             L.tpz_debug_table_runs_entries.argtypes = \
                 list(L.tpz_table_runs_entries.argtypes[:-1]) + [C.c_uint32, C.c_void_p]
@@ -577,6 +598,74 @@ class Context:
                                   C.c_void_p(d_key_pos), n_keys, C.c_void_p(d_block),
                                   C.c_void_p(d_entry), C.c_void_p(d_status), C.c_void_p(d_valid),
                                   C.c_void_p(stream)), "tpz_seek_keys")
+
+    def raw_verify_ptrs(self, d_src: int, d_ext: int, n_blocks: int, src_bytes: int,
+                        d_status: int, d_crc: int, stream: int = 0) -> None:
+        """tpz_raw_verify: Block::decode's checks ahead of the entries (tag, CRC, n and the
+        offsets readable) for every block of the batch; no decoded bytes anywhere."""
+        b = Batch(d_src, d_ext, n_blocks, src_bytes)
+        check(lib().tpz_raw_verify(self.handle, C.byref(b), C.c_void_p(d_status),
+                                   C.c_void_p(d_crc), C.c_void_p(stream)), "tpz_raw_verify")
+
+    def raw_seek_keys_ptrs(self, table: RawTable, d_keys: int, d_key_pos: int, n_keys: int,
+                           d_block: int, d_entry: int, d_status: int, d_valid: int,
+                           stream: int = 0) -> None:
+        """tpz_raw_seek_keys: tpz_seek_keys over an in-place table."""
+        check(lib().tpz_raw_seek_keys(self.handle, C.byref(table), C.c_void_p(d_keys),
+                                      C.c_void_p(d_key_pos), n_keys, C.c_void_p(d_block),
+                                      C.c_void_p(d_entry), C.c_void_p(d_status),
+                                      C.c_void_p(d_valid), C.c_void_p(stream)),
+              "tpz_raw_seek_keys")
+
+    def raw_get_keys_ptrs(self, d_tables: int, n_tables: int, h_level_first: int, n_levels: int,
+                          d_keys: int, d_key_pos: int, n_keys: int, d_result: int, d_status: int,
+                          d_table: int, d_block: int, d_entry: int, d_val_pos: int,
+                          stream: int = 0) -> None:
+        """tpz_raw_get_keys: tpz_get_keys over the n_tables tpz_raw_table descriptors at
+        d_tables."""
+        check(lib().tpz_raw_get_keys(self.handle, C.c_void_p(d_tables), n_tables,
+                                     C.c_void_p(h_level_first), n_levels, C.c_void_p(d_keys),
+                                     C.c_void_p(d_key_pos), n_keys, C.c_void_p(d_result),
+                                     C.c_void_p(d_status), C.c_void_p(d_table),
+                                     C.c_void_p(d_block), C.c_void_p(d_entry),
+                                     C.c_void_p(d_val_pos), C.c_void_p(stream)),
+              "tpz_raw_get_keys")
+
+    def raw_get_values_ptrs(self, d_tables: int, n_tables: int, n_keys: int, d_result: int,
+                            d_table: int, d_block: int, d_entry: int, d_val_pos: int, d_vals: int,
+                            val_cap: int, stream: int = 0) -> None:
+        """tpz_raw_get_values: the values of tpz_raw_get_keys' FOUND queries."""
+        check(lib().tpz_raw_get_values(self.handle, C.c_void_p(d_tables), n_tables, n_keys,
+                                       C.c_void_p(d_result), C.c_void_p(d_table),
+                                       C.c_void_p(d_block), C.c_void_p(d_entry),
+                                       C.c_void_p(d_val_pos), C.c_void_p(d_vals), val_cap,
+                                       C.c_void_p(stream)), "tpz_raw_get_values")
+
+    def raw_lsm_get_keys_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                              h_level_first: int, n_levels: int, d_keys: int, d_key_pos: int,
+                              n_keys: int, d_result: int, d_status: int, d_table: int,
+                              d_block: int, d_entry: int, d_val_pos: int, stream: int = 0) -> None:
+        """tpz_raw_lsm_get_keys: tpz_lsm_get_keys with in-place tables under the runs."""
+        check(lib().tpz_raw_lsm_get_keys(self.handle, C.c_void_p(d_runs), n_runs,
+                                         C.c_void_p(d_tables), n_tables,
+                                         C.c_void_p(h_level_first), n_levels, C.c_void_p(d_keys),
+                                         C.c_void_p(d_key_pos), n_keys, C.c_void_p(d_result),
+                                         C.c_void_p(d_status), C.c_void_p(d_table),
+                                         C.c_void_p(d_block), C.c_void_p(d_entry),
+                                         C.c_void_p(d_val_pos), C.c_void_p(stream)),
+              "tpz_raw_lsm_get_keys")
+
+    def raw_lsm_get_values_ptrs(self, d_runs: int, n_runs: int, d_tables: int, n_tables: int,
+                                n_keys: int, d_result: int, d_table: int, d_block: int,
+                                d_entry: int, d_val_pos: int, d_vals: int, val_cap: int,
+                                stream: int = 0) -> None:
+        """tpz_raw_lsm_get_values: the values of tpz_raw_lsm_get_keys' FOUND queries."""
+        check(lib().tpz_raw_lsm_get_values(self.handle, C.c_void_p(d_runs), n_runs,
+                                           C.c_void_p(d_tables), n_tables, n_keys,
+                                           C.c_void_p(d_result), C.c_void_p(d_table),
+                                           C.c_void_p(d_block), C.c_void_p(d_entry),
+                                           C.c_void_p(d_val_pos), C.c_void_p(d_vals), val_cap,
+                                           C.c_void_p(stream)), "tpz_raw_lsm_get_values")
 
     def bloom_ptrs(self, d_filter: int, filter_len: int, d_keys: int, d_key_pos: int,
                    n_keys: int, d_out: int, stream: int = 0) -> None:

@@ -36,7 +36,7 @@ from ._lib import Context
 from .batch import DeviceBatch, FlatColumns, decode_flat, decompress_batch
 from .encode import (DeviceEntries, EntryError, compress_blocks, compress_bound, encode_blocks_async,
                      encode_bound, plan_blocks_async)
-from .table import BlockError, DeviceTable, ReferencePanic, open_images
+from .table import BlockError, DeviceTable, RawTable, ReferencePanic, open_images
 
 
 def _dev(device: int) -> torch.device:
@@ -118,6 +118,8 @@ def entries_from_tables(ctx: Context, tables, check: bool = True,
     dev = _dev(ctx.device)
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     tables = list(tables)
+    if any(isinstance(t, RawTable) for t in tables):
+        raise ValueError("in-place tables answer gets; compaction inputs need DeviceTables")
     n_runs = len(tables)
     if n_runs > _lib.MERGE_MAX_RUNS:
         raise ValueError(f"{n_runs} tables: tpz_merge_runs takes at most {_lib.MERGE_MAX_RUNS} runs")
@@ -165,7 +167,7 @@ def _merge_inputs(ctx: Context, regions, stream: torch.cuda.Stream | None) -> De
     entries_from_tables (no host concatenation, upload or decode), (bytes, extents) tuples through
     _merge_regions; then one tpz_merge_runs over a run per table."""
     regions = list(regions)
-    resident = [isinstance(r, DeviceTable) for r in regions]
+    resident = [isinstance(r, (DeviceTable, RawTable)) for r in regions]
     if regions and all(resident):
         ent, run_first = entries_from_tables(ctx, regions, stream=stream)
         return merge_runs(ctx, ent, run_first, stream)[0]
@@ -250,18 +252,20 @@ class TaskTables(list):
     arena: torch.Tensor
     entries: DeviceEntries
 
-    def open(self, ctx: Context, verify: bool = False, strict: bool = True) -> list:
+    def open(self, ctx: Context, verify: bool = False, strict: bool = True,
+             raw: bool = False) -> list:
         """The task's output tables as resident DeviceTables, in this list's order, opened where
         their images lie (table.open_images: no D2H, host parse or upload); ready for
         DeviceLevels(ctx, levels) / DeviceLsm. verify: the whole-file CRC check first (the images
-        were written by this process: off by default)."""
+        were written by this process: off by default). raw: as in-place RawTables (gets only, no
+        decoded columns)."""
         if not len(self):
             return []
         base = self.arena.data_ptr()
         order = sorted(range(len(self)), key=lambda i: self[i].image.data_ptr())
         got = open_images(ctx, self.arena,
                           [(self[i].image.data_ptr() - base, self[i].size) for i in order],
-                          verify, strict)
+                          verify, strict, raw)
         out = [None] * len(self)
         for i, t in zip(order, got):
             out[i] = t
@@ -565,10 +569,10 @@ def _flush_runs(ctx: Context, runs, block_size: int, codec: int, false_positive_
     return t, merged
 
 
-def open_output(ctx: Context, table, verify: bool = False):
+def open_output(ctx: Context, table, verify: bool = False, raw: bool = False):
     """flush_runs' OutputTable as a resident DeviceTable, opened where its image lies
     (table.open_images); the L0 table a flush just wrote goes straight into DeviceLsm."""
-    return open_images(ctx, table.image, [(0, table.size)], verify)[0]
+    return open_images(ctx, table.image, [(0, table.size)], verify, raw=raw)[0]
 
 
 def flush_like_start_flush(ctx: Context, view, block_size: int = 4096, codec: int = 1,

@@ -1069,6 +1069,7 @@ static bool level_first_ok(const uint32_t* h, uint32_t n_levels, uint32_t n_tabl
 }
 
 using tpz::Flavour;
+using tpz::TableKind;
 
 // tpz_lsm_* / tpz_level_scan_*: d_runs holds n_runs <= TPZ_MEM_MAX_RUNS descriptors (the tables'
 // calls pass none).
@@ -1078,8 +1079,8 @@ static bool runs_ok(const tpz_mem_run* d_runs, uint32_t n_runs) {
 
 // The query calls: one implementation per operation, the exported calls below forward to it with
 // their flavour (tables: no runs). Every argument check precedes hipSetDevice.
-static tpz_err get_keys(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
-                        const tpz_get_table* d_tables, uint32_t n_tables,
+static tpz_err get_keys(Flavour f, TableKind k, tpz_ctx* c, const tpz_mem_run* d_runs,
+                        uint32_t n_runs, const void* d_tables, uint32_t n_tables,
                         const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
                         const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
                         uint8_t* d_status, uint32_t* d_table, uint32_t* d_block, uint32_t* d_entry,
@@ -1101,7 +1102,7 @@ static tpz_err get_keys(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32
   uint64_t* part = nullptr;
   tpz_err r = ws_buffer(c, stream, kWsGet, 8 * (tpz::flat_scan_parts_words(n_keys) / 3), &part);
   if (r != TPZ_SUCCESS) return r;
-  tpz::GetLaunch a{f, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels, d_keys,
+  tpz::GetLaunch a{f, k, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels, d_keys,
                    d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry, d_val_pos,
                    part};
   tpz::launch_get_walk(a, s);
@@ -1109,8 +1110,8 @@ static tpz_err get_keys(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32
   return TPZ_SUCCESS;
 }
 
-static tpz_err get_values(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
-                          const tpz_get_table* d_tables, uint32_t n_tables, uint32_t n_keys,
+static tpz_err get_values(Flavour f, TableKind k, tpz_ctx* c, const tpz_mem_run* d_runs,
+                          uint32_t n_runs, const void* d_tables, uint32_t n_tables, uint32_t n_keys,
                           const uint8_t* d_result, const uint32_t* d_table, const uint32_t* d_block,
                           const uint32_t* d_entry, const uint64_t* d_val_pos, uint8_t* d_vals,
                           uint64_t val_cap, void* stream) {
@@ -1122,7 +1123,7 @@ static tpz_err get_values(Flavour f, tpz_ctx* c, const tpz_mem_run* d_runs, uint
     return TPZ_ERR_INVALID_ARG;
   if (n_keys == 0 || val_cap == 0) return TPZ_SUCCESS;
   TPZ_HIP(hipSetDevice(c->device));
-  tpz::GetGatherLaunch a{f, d_runs, n_runs, d_tables, n_tables, n_keys, d_result, d_table, d_block,
+  tpz::GetGatherLaunch a{f, k, d_runs, n_runs, d_tables, n_tables, n_keys, d_result, d_table, d_block,
                          d_entry, d_val_pos, d_vals, val_cap};
   tpz::launch_get_gather(a, (hipStream_t)stream);
   TPZ_HIP(hipGetLastError());
@@ -1236,8 +1237,8 @@ tpz_err tpz_get_keys(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_table
                      const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
                      uint8_t* d_status, uint32_t* d_table, uint32_t* d_block, uint32_t* d_entry,
                      uint64_t* d_val_pos, void* stream) {
-  return get_keys(Flavour::kTables, c, nullptr, 0, d_tables, n_tables, h_level_first, n_levels,
-                  d_keys, d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry,
+  return get_keys(Flavour::kTables, TableKind::kDecoded, c, nullptr, 0, d_tables, n_tables,
+                  h_level_first, n_levels, d_keys, d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry,
                   d_val_pos, stream);
 }
 
@@ -1245,8 +1246,8 @@ tpz_err tpz_get_values(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tab
                        uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
                        const uint32_t* d_block, const uint32_t* d_entry, const uint64_t* d_val_pos,
                        uint8_t* d_vals, uint64_t val_cap, void* stream) {
-  return get_values(Flavour::kTables, c, nullptr, 0, d_tables, n_tables, n_keys, d_result, d_table,
-                    d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
+  return get_values(Flavour::kTables, TableKind::kDecoded, c, nullptr, 0, d_tables, n_tables,
+                    n_keys, d_result, d_table, d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
 }
 
 tpz_err tpz_mem_prefix(tpz_ctx* c, const tpz_entries* entries, uint64_t* d_prefix, void* stream) {
@@ -1267,8 +1268,8 @@ tpz_err tpz_lsm_get_keys(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
                          const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
                          uint8_t* d_status, uint32_t* d_table, uint32_t* d_block,
                          uint32_t* d_entry, uint64_t* d_val_pos, void* stream) {
-  return get_keys(Flavour::kLsm, c, d_runs, n_runs, d_tables, n_tables, h_level_first, n_levels,
-                  d_keys, d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry,
+  return get_keys(Flavour::kLsm, TableKind::kDecoded, c, d_runs, n_runs, d_tables, n_tables,
+                  h_level_first, n_levels, d_keys, d_key_pos, n_keys, d_result, d_status, d_table, d_block, d_entry,
                   d_val_pos, stream);
 }
 
@@ -1278,8 +1279,79 @@ tpz_err tpz_lsm_get_values(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_run
                            const uint32_t* d_block, const uint32_t* d_entry,
                            const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
                            void* stream) {
-  return get_values(Flavour::kLsm, c, d_runs, n_runs, d_tables, n_tables, n_keys, d_result,
-                    d_table, d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
+  return get_values(Flavour::kLsm, TableKind::kDecoded, c, d_runs, n_runs, d_tables, n_tables,
+                    n_keys, d_result, d_table, d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
+}
+
+// ---- in-place tables (tpz_raw.hip): the same host paths with TableKind::kRaw.
+tpz_err tpz_raw_verify(tpz_ctx* c, const tpz_batch* b, uint8_t* d_status, uint32_t* d_crc,
+                       void* stream) {
+  if (!d_status || ((uintptr_t)d_crc & 3u)) return TPZ_ERR_INVALID_ARG;
+  // the payload CRCs: the range CRC with the 5-byte trailer (crc u32 BE | tag), which also leaves
+  // OK / CHECKSUM_MISMATCH / MALFORMED (shorter than 5 bytes) in d_status
+  tpz_err r = crc_ranges(c, b, 5, d_crc, d_status, stream);
+  if (r != TPZ_SUCCESS || b->n_blocks == 0) return r;
+  tpz::launch_raw_verify_headers(b->d_src, b->d_ext, b->n_blocks, d_status, d_crc,
+                                 (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_raw_seek_keys(tpz_ctx* c, const tpz_raw_table* t, const uint8_t* d_keys,
+                          const uint64_t* d_key_pos, uint32_t n_keys, uint32_t* d_block,
+                          uint32_t* d_entry, uint8_t* d_status, uint8_t* d_valid, void* stream) {
+  if (!c || !t || !d_key_pos || !d_block || !d_entry || !d_status || !d_valid)
+    return TPZ_ERR_INVALID_ARG;
+  if (n_keys == 0) return TPZ_SUCCESS;
+  if (t->n_blocks && (!t->d_first_keys || !t->d_first_pos || !t->d_ext || !t->d_src ||
+                      !t->d_status))
+    return TPZ_ERR_INVALID_ARG;
+  TPZ_HIP(hipSetDevice(c->device));
+  tpz::RawSeekLaunch a{*t, d_keys, d_key_pos, n_keys, d_block, d_entry, d_status, d_valid};
+  tpz::launch_raw_seek(a, (hipStream_t)stream);
+  TPZ_HIP(hipGetLastError());
+  return TPZ_SUCCESS;
+}
+
+tpz_err tpz_raw_get_keys(tpz_ctx* c, const tpz_raw_table* d_tables, uint32_t n_tables,
+                         const uint32_t* h_level_first, uint32_t n_levels, const uint8_t* d_keys,
+                         const uint64_t* d_key_pos, uint32_t n_keys, uint8_t* d_result,
+                         uint8_t* d_status, uint32_t* d_table, uint32_t* d_block,
+                         uint32_t* d_entry, uint64_t* d_val_pos, void* stream) {
+  return get_keys(Flavour::kTables, TableKind::kRaw, c, nullptr, 0, d_tables, n_tables,
+                  h_level_first, n_levels, d_keys, d_key_pos, n_keys, d_result, d_status, d_table,
+                  d_block, d_entry, d_val_pos, stream);
+}
+
+tpz_err tpz_raw_get_values(tpz_ctx* c, const tpz_raw_table* d_tables, uint32_t n_tables,
+                           uint32_t n_keys, const uint8_t* d_result, const uint32_t* d_table,
+                           const uint32_t* d_block, const uint32_t* d_entry,
+                           const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
+                           void* stream) {
+  return get_values(Flavour::kTables, TableKind::kRaw, c, nullptr, 0, d_tables, n_tables, n_keys,
+                    d_result, d_table, d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
+}
+
+tpz_err tpz_raw_lsm_get_keys(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                             const tpz_raw_table* d_tables, uint32_t n_tables,
+                             const uint32_t* h_level_first, uint32_t n_levels,
+                             const uint8_t* d_keys, const uint64_t* d_key_pos, uint32_t n_keys,
+                             uint8_t* d_result, uint8_t* d_status, uint32_t* d_table,
+                             uint32_t* d_block, uint32_t* d_entry, uint64_t* d_val_pos,
+                             void* stream) {
+  return get_keys(Flavour::kLsm, TableKind::kRaw, c, d_runs, n_runs, d_tables, n_tables,
+                  h_level_first, n_levels, d_keys, d_key_pos, n_keys, d_result, d_status, d_table,
+                  d_block, d_entry, d_val_pos, stream);
+}
+
+tpz_err tpz_raw_lsm_get_values(tpz_ctx* c, const tpz_mem_run* d_runs, uint32_t n_runs,
+                               const tpz_raw_table* d_tables, uint32_t n_tables, uint32_t n_keys,
+                               const uint8_t* d_result, const uint32_t* d_table,
+                               const uint32_t* d_block, const uint32_t* d_entry,
+                               const uint64_t* d_val_pos, uint8_t* d_vals, uint64_t val_cap,
+                               void* stream) {
+  return get_values(Flavour::kLsm, TableKind::kRaw, c, d_runs, n_runs, d_tables, n_tables, n_keys,
+                    d_result, d_table, d_block, d_entry, d_val_pos, d_vals, val_cap, stream);
 }
 
 tpz_err tpz_scan_ranges(tpz_ctx* c, const tpz_get_table* d_tables, uint32_t n_tables,

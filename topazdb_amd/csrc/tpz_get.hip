@@ -111,8 +111,9 @@ __global__ __launch_bounds__(256) void lsm_get_gather_kernel(LsmGatherParams p) 
 }  // namespace
 
 void launch_get_walk(const GetLaunch& a, hipStream_t stream) {
+  if (a.kind == TableKind::kRaw) return launch_raw_get_walk(a, stream);   // tpz_raw.hip
   WalkParams p{};
-  p.tabs = a.tabs;
+  p.tabs = static_cast<const tpz_get_table*>(a.tabs);
   p.n_tables = a.n_tables;
   p.n_levels = a.n_levels;
   for (u32 l = 0; l <= TPZ_GET_MAX_LEVELS; l++)
@@ -135,7 +136,8 @@ void launch_get_walk(const GetLaunch& a, hipStream_t stream) {
 }
 
 void launch_get_gather(const GetGatherLaunch& a, hipStream_t stream) {
-  const GatherParams p{a.tabs, a.n_tables, a.n_q, a.result, a.table, a.block, a.entry, a.val_pos,
+  if (a.kind == TableKind::kRaw) return launch_raw_get_gather(a, stream);   // tpz_raw.hip
+  const GatherParams p{static_cast<const tpz_get_table*>(a.tabs), a.n_tables, a.n_q, a.result, a.table, a.block, a.entry, a.val_pos,
                        a.vals, a.val_cap};
   const dim3 grid((a.n_q + 255) / 256);
   if (a.flavour == Flavour::kLsm) {

@@ -5,9 +5,11 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "tpz_copy.h"
 #include "tpz_internal.h"
+#include "tpz_raw_dev.h"
 #include "tpz_seek_dev.h"
 #include "tpz_xxh3.h"
 
@@ -64,12 +66,13 @@ struct WalkOut {
 
 // tables[lo .. hi): partition_point(smallest_key <= key).saturating_sub(1) (level.rs:449-451);
 // smallest_key = block_metas[0].first_key (table.rs:143-151). lo < hi.
-__device__ __forceinline__ u32 level_table(const tpz_get_table* tabs, u32 lo, u32 hi,
-                                           const uint8_t* qk, u64 ql) {
+template <class G>
+__device__ __forceinline__ u32 level_table(const G* tabs, u32 lo, u32 hi, const uint8_t* qk,
+                                           u64 ql) {
   const u32 first = lo;
   while (lo < hi) {
     const u32 mid = lo + (hi - lo) / 2;
-    const tpz_table& t = tabs[mid].table;
+    const auto& t = table_of(tabs[mid]);
     u64 a = 0, len = 0;
     if (t.n_blocks) {           // (a table without blocks cannot be opened: its key reads empty)
       a = t.d_first_pos[0];
@@ -83,15 +86,18 @@ __device__ __forceinline__ u32 level_table(const tpz_get_table* tabs, u32 lo, u3
 // Does any table of the set have a filter? The whole wave looks, a lane per table, before the
 // lanes past the last query leave: the vote must not depend on how many lanes have a query (the
 // last wave of a launch may hold one).
-__device__ __forceinline__ bool any_filter(const WalkParams& p) {
+template <class P>
+__device__ __forceinline__ bool any_filter(const P& p) {
   bool filters = false;
   for (u32 t = copydev::lane_id(); t < p.n_tables; t += 64) filters |= p.tabs[t].d_filter != nullptr;
   return __any(filters);
 }
 
-// The walk over L0 and the levels for the key qk[0 .. ql); `o` holds ABSENT on entry.
-__device__ __forceinline__ void walk(const WalkParams& p, const uint8_t* qk, u64 ql,
-                                     bool any_filter, WalkOut& o) {
+// The walk over L0 and the levels for the key qk[0 .. ql); `o` holds ABSENT on entry. P is
+// WalkParams, or RawWalkParams over in-place tables (tpz_raw_dev.h).
+template <class P>
+__device__ __forceinline__ void walk(const P& p, const uint8_t* qk, u64 ql, bool any_filter,
+                                     WalkOut& o) {
   const u32 l0 = p.n_levels ? p.level_first[1] : 0u;               // L0 = tables [0, l0)
   const u32 steps = p.n_levels ? l0 + (p.n_levels - 1) : 0u;       // L0's tables, then a level each
   const u64 h = any_filter ? xxh3::hash64(qk, ql) : 0;   // xxh3_64(key) for may_contain, once
@@ -105,7 +111,7 @@ __device__ __forceinline__ void walk(const WalkParams& p, const uint8_t* qk, u64
       if (lo >= hi) continue;                   // :446-448: an empty level
       t = level_table(p.tabs, lo, hi, qk, ql);
     }
-    const tpz_get_table& g = p.tabs[t];
+    const auto& g = p.tabs[t];
     const uint8_t* filter = g.d_filter;
     if (filter) {                               // may_contain (table.rs:114-119)
       const u32 pr = seekdev::bloom_probe(filter, g.filter_len, h);
@@ -117,7 +123,8 @@ __device__ __forceinline__ void walk(const WalkParams& p, const uint8_t* qk, u64
         break;
       }
     }
-    const seekdev::SeekPos r = seekdev::seek_table(g.table, qk, ql);
+    const auto& tab = table_of(g);
+    const seekdev::SeekPos r = seekdev::seek_table(tab, qk, ql);
     if (r.status != TPZ_BLOCK_OK) {             // create_and_seek_to_key(..)? / its panics
       o.res = TPZ_GET_ERROR;
       o.st = r.status;
@@ -128,11 +135,11 @@ __device__ __forceinline__ void walk(const WalkParams& p, const uint8_t* qk, u64
     }
     if (!r.valid) continue;
     // iter.key() == key (:435): the iterator is valid, so its block decoded and holds the entry
-    const seekdev::BlockView v = seekdev::block_view(g.table, r.block, g.table.d_status[r.block]);
+    const auto v = seekdev::block_view(tab, r.block, tab.d_status[r.block]);
     u64 kl;
     const uint8_t* k = seekdev::entry_key(v, r.entry, kl);
     if (kl != ql || seekdev::key_cmp(k, kl, qk, ql) != 0) continue;
-    seekdev::entry_value(v, g.table.d_count[r.block], r.entry, o.vlen);
+    seekdev::entry_value(v, seekdev::block_count(tab, r.block), r.entry, o.vlen);
     o.res = o.vlen ? TPZ_GET_FOUND : TPZ_GET_DELETED;   // :436-439: an empty value is a tombstone
     o.tb = t;
     o.blk = r.block;
@@ -141,7 +148,8 @@ __device__ __forceinline__ void walk(const WalkParams& p, const uint8_t* qk, u64
   }
 }
 
-__device__ __forceinline__ void store(const WalkParams& p, u32 i, const WalkOut& o) {
+template <class P>
+__device__ __forceinline__ void store(const P& p, u32 i, const WalkOut& o) {
   p.result[i] = (uint8_t)o.res;
   p.status[i] = (uint8_t)o.st;
   p.table[i] = o.tb;
@@ -152,15 +160,20 @@ __device__ __forceinline__ void store(const WalkParams& p, u32 i, const WalkOut&
 
 // The value of entry j of block b of table t, each checked against the descriptors: null and
 // len = 0 where one is out of range or the block did not decode.
-__device__ __forceinline__ const uint8_t* table_value(const tpz_get_table* tabs, u32 n_tables,
-                                                      u32 t, u32 b, u32 j, u64& len) {
+template <class G>
+__device__ __forceinline__ const uint8_t* table_value(const G* tabs, u32 n_tables, u32 t, u32 b,
+                                                      u32 j, u64& len) {
   if (t < n_tables) {
-    const tpz_table& tab = tabs[t].table;
+    const auto& tab = table_of(tabs[t]);
     if (b < tab.n_blocks) {
       const u32 st = tab.d_status[b];
-      const u32 n = tab.d_count[b];
+      // (the decoded count is read here, not through block_count: behind the call this load
+      // comes out as a flat load in the gather kernels of tpz_get.hip)
+      u32 n;
+      if constexpr (std::is_same<G, tpz_get_table>::value) n = tab.d_count[b];
+      else n = seekdev::block_count(tab, b);
       if (block_decoded(st) && j < n) {
-        const seekdev::BlockView v = seekdev::block_view(tab, b, st);
+        const auto v = seekdev::block_view(tab, b, st);
         return seekdev::entry_value(v, n, j, len);
       }
     }

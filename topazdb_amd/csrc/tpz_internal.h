@@ -216,7 +216,8 @@ struct CrcLaunch {
   const uint64_t* ext;
   uint64_t src_bytes;
   uint32_t n_ranges;
-  uint32_t trailer;       // 0 (plain ranges) or 4 (FileObject: BE u32 trailer after the CRC)
+  uint32_t trailer;       // 0 (plain ranges), 4 (FileObject: BE u32 trailer after the CRC) or 5
+                          // (a block: the BE u32 CRC and the tag byte, tpz_raw_verify)
   const uint32_t* tables; // kRangeTables x 256
   const uint32_t* rep;    // kCrcRepWords
   uint32_t* acc;          // workspace: n_ranges, zeroed before the launch
@@ -381,15 +382,20 @@ hipError_t launch_wal_entries(const WalEntriesLaunch& a, hipStream_t stream);
 // the kernels and is never inferred from n_runs: the lsm kernels run with no runs too (they apply
 // LsmStorage::get's empty-key assert, which tpz_get_keys does not).
 enum class Flavour : uint32_t { kTables, kLsm, kLevel };
+// Which kind of resident table a get launch reads: decoded columns (tpz_get_table) or the encoded
+// blocks in place (tpz_raw_table; the kernels of tpz_raw.hip). It travels beside the flavour and
+// is never inferred from the pointers.
+enum class TableKind : uint32_t { kDecoded, kRaw };
 
 // tpz_get_keys / tpz_get_values / tpz_lsm_get_keys / tpz_lsm_get_values (tpz_get.hip; the lsm
 // walk's kernel is tpz_mem.hip's): LevelController::get over resident tables, and LsmStorage::get
 // over memtable runs plus them.
 struct GetLaunch {
   Flavour flavour;              // kTables / kLsm
+  TableKind kind;
   const tpz_mem_run* runs;      // device (kLsm)
   uint32_t n_runs;              // <= TPZ_MEM_MAX_RUNS
-  const tpz_get_table* tabs;    // device
+  const void* tabs;             // device: tpz_get_table (kDecoded) or tpz_raw_table (kRaw)
   uint32_t n_tables;
   const uint32_t* level_first;  // host: n_levels + 1, checked by the caller
   uint32_t n_levels;            // <= TPZ_GET_MAX_LEVELS
@@ -407,9 +413,10 @@ struct GetLaunch {
 void launch_get_walk(const GetLaunch& a, hipStream_t stream);
 struct GetGatherLaunch {
   Flavour flavour;              // kTables / kLsm
+  TableKind kind;
   const tpz_mem_run* runs;
   uint32_t n_runs;
-  const tpz_get_table* tabs;
+  const void* tabs;             // tpz_get_table (kDecoded) or tpz_raw_table (kRaw)
   uint32_t n_tables;
   uint32_t n_q;                 // > 0
   const uint8_t* result;
@@ -421,6 +428,24 @@ struct GetGatherLaunch {
   uint64_t val_cap;
 };
 void launch_get_gather(const GetGatherLaunch& a, hipStream_t stream);
+// The same over in-place tables (tpz_raw.hip; a.kind == kRaw: launch_get_walk / launch_get_gather
+// hand over to them), tpz_raw_seek_keys, and tpz_raw_verify's header checks after the range CRC
+// (launch_crc_ranges with trailer 5 left its CRCs and OK / CHECKSUM_MISMATCH / MALFORMED).
+void launch_raw_get_walk(const GetLaunch& a, hipStream_t stream);
+void launch_raw_get_gather(const GetGatherLaunch& a, hipStream_t stream);
+struct RawSeekLaunch {
+  tpz_raw_table t;
+  const uint8_t* q;
+  const uint64_t* q_pos;
+  uint32_t n_q;                 // > 0
+  uint32_t* out_block;
+  uint32_t* out_entry;
+  uint8_t* out_status;
+  uint8_t* out_valid;
+};
+void launch_raw_seek(const RawSeekLaunch& a, hipStream_t stream);
+void launch_raw_verify_headers(const uint8_t* src, const uint64_t* ext, uint32_t n_blocks,
+                               uint8_t* status, uint32_t* crc, hipStream_t stream);
 
 // tpz_mem_prefix (tpz_mem.hip): the prefix column of a memtable run resident in HBM.
 void launch_mem_prefix(const tpz_entries& e, uint64_t* prefix, hipStream_t stream);   // n_entries > 0

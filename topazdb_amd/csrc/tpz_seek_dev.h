@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "tpz_internal.h"
+#include "tpz_raw_dev.h"   // the in-place view's overloads, ahead of the templates below
 
 namespace tpz {
 namespace seekdev {
@@ -50,6 +51,7 @@ __device__ __forceinline__ BlockView block_view(const tpz_table& t, u32 b, u32 s
   return BlockView{t.d_ends + 2 * ends_base(t.d_entry_first, e0, b), t.d_data + slot_base(e0, b),
                    nullptr};
 }
+__device__ __forceinline__ u32 block_count(const tpz_table& t, u32 b) { return t.d_count[b]; }
 // Entry j's key: its bytes and length.
 __device__ __forceinline__ const uint8_t* entry_key(const BlockView& v, u32 j, u64& len) {
   const u32 lo = j ? v.ends[2 * (j - 1)] : 0u, hi = v.ends[2 * j];
@@ -72,8 +74,10 @@ struct SeekPos {
   bool valid;   // is_valid(): the current key is non-empty
 };
 
-// SsTableIterator::seek_to_key (src/table/iterator.rs:44-72) for the key qk[0 .. ql).
-__device__ __forceinline__ SeekPos seek_table(const tpz_table& t, const uint8_t* qk, u64 ql) {
+// SsTableIterator::seek_to_key (src/table/iterator.rs:44-72) for the key qk[0 .. ql), over a
+// decoded table (tpz_table) or an in-place one (tpz_raw_table, tpz_raw_dev.h).
+template <class Table>
+__device__ __forceinline__ SeekPos seek_table(const Table& t, const uint8_t* qk, u64 ql) {
   const u32 n_blocks = t.n_blocks;
   if (n_blocks == 0)                          // block_metas[0]: the reference panics
     return SeekPos{0, 0, TPZ_BLOCK_MALFORMED, false};
@@ -93,8 +97,8 @@ __device__ __forceinline__ SeekPos seek_table(const tpz_table& t, const uint8_t*
   bool valid = false, panic = false;
   if (block_decoded(st)) {
     // BlockIterator::seek_to_key
-    const BlockView v = block_view(t, b, st);
-    const u32 n = t.d_count[b];
+    const auto v = block_view(t, b, st);
+    const u32 n = block_count(t, b);
     u32 l = 0, r = n;
     pos = n;
     bool found = false;
@@ -118,8 +122,8 @@ __device__ __forceinline__ SeekPos seek_table(const tpz_table& t, const uint8_t*
       st = t.d_status[b];
       pos = 0;
       valid = false;
-      if (block_decoded(st) && t.d_count[b] > 0) {
-        const BlockView w = block_view(t, b, st);
+      if (block_decoded(st) && block_count(t, b) > 0) {
+        const auto w = block_view(t, b, st);
         panic = w.seek_panics(0);
         entry_key(w, 0, kl);
         valid = !panic && kl > 0;

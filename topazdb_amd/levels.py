@@ -42,11 +42,11 @@ from . import _lib
 from ._lib import (BLOCK_MALFORMED, BOUND_AFTER, BOUND_EXCLUDED, BOUND_INCLUDED, BOUND_UNBOUNDED,
                    GET_ABSENT, GET_DELETED, GET_ERROR, GET_FOUND, GET_NONE, SCAN_ERROR, SCAN_MORE,
                    Context, Entries, GetTable, MemRun)
-from .table import DeviceTable, ReferencePanic, _pack
+from .table import RAW_SCAN_ERROR, DeviceTable, RawTable, ReferencePanic, _pack
 
 
-def _device_table(t) -> DeviceTable:
-    return t if isinstance(t, DeviceTable) else t.device
+def _device_table(t):
+    return t if isinstance(t, (DeviceTable, RawTable)) else t.device
 
 
 _KINDS = {"in": BOUND_INCLUDED, "ex": BOUND_EXCLUDED, "after": BOUND_AFTER}
@@ -126,13 +126,18 @@ class DeviceLevels:
         self.n_levels = len(self.levels)
         # the level scan's cursors: one per L0 table and per non-empty level below L0
         self.n_cursors = sum(len(lv) if i == 0 else bool(lv) for i, lv in enumerate(self.levels))
-        desc = (GetTable * max(self.n_tables, 1))()
+        # a set of in-place tables (RawTable) answers gets with the tpz_raw_* calls
+        kinds = {isinstance(_device_table(t), RawTable) for t in self.tables}
+        if len(kinds) > 1:
+            raise TypeError("a level set holds DeviceTables or RawTables, not both")
+        self.raw = kinds == {True}
+        desc = ((_lib.RawTable if self.raw else GetTable) * max(self.n_tables, 1))()
         for i, t in enumerate(self.tables):
             dt = _device_table(t)
             if dt is None:
                 raise ValueError(f"table {i} has no resident DeviceTable (SsTable.open keeps one)")
-            desc[i] = GetTable(dt.table(), dt.bloom.data_ptr() if dt.bloom is not None else None,
-                               dt.bloom_len)
+            desc[i] = dt.raw_table() if self.raw else GetTable(
+                dt.table(), dt.bloom.data_ptr() if dt.bloom is not None else None, dt.bloom_len)
         raw = np.frombuffer(bytes(desc), np.uint8).copy()
         self.d_tables = torch.from_numpy(raw).to(self.dev)       # uploaded once
 
@@ -146,8 +151,14 @@ class DeviceLevels:
 
     def _call(self, op: str, by_level: bool, *args) -> None:
         """tpz_<family><op> over the tables (the lsm family: the runs in front), or with
-        by_level (scans only) tpz_level_<op> over the runs and the tables."""
-        if by_level:
+        by_level (scans only) tpz_level_<op> over the runs and the tables. Over in-place tables
+        the gets are tpz_raw_<family><op>; the scans need DeviceTables."""
+        if self.raw:
+            if not op.startswith("get_"):
+                raise ValueError(RAW_SCAN_ERROR)
+            getattr(self.ctx, f"raw_{self._family}{op}_ptrs")(
+                *(self._runs() if self._family else ()), *args)
+        elif by_level:
             getattr(self.ctx, f"level_{op}_ptrs")(*self._runs(), *args)
         elif self._family:
             getattr(self.ctx, f"{self._family}{op}_ptrs")(*self._runs(), *args)
@@ -296,7 +307,8 @@ class DeviceLevels:
             return ReferencePanic("attempt to calculate the remainder with a divisor of zero")
         if _device_table(self.tables[table]).n_blocks == 0:       # block_metas[0]
             return ReferencePanic("index out of bounds: the len is 0 but the index is 0")
-        r = self._host_block(table, block)
+        t = _device_table(self.tables[table])
+        r = t.block_error(block) if self.raw else self._host_block(table, block)
         if isinstance(r, Exception):                 # read_block_cached's Err / decode's panic
             return r
         assert status == BLOCK_MALFORMED, status

@@ -335,6 +335,143 @@ class DeviceTable:
         return out
 
 
+RAW_SCAN_ERROR = "in-place tables answer gets; scans need DeviceTables"
+
+
+class RawTable:
+    """An in-place table: the device side of an SST data region served for point gets from its
+    encoded blocks where they lie, with no decoded columns (tpz_raw_table). The codec step runs
+    first where some block is snappy or lz4 (its output is the Uncompress form the view reads),
+    then tpz_raw_verify: Block::decode's checks ahead of the entries (the tag, the CRC, n and the
+    offsets readable). `seek_keys` and `may_contain` are DeviceTable's; scans and compaction
+    inputs need a DeviceTable."""
+
+    def __init__(self, ctx: Context, region: bytes, ext: np.ndarray,
+                 first_keys: list[bytes] | None = None, bloom: bytes | None = None):
+        self.ctx = ctx
+        dev = torch.device("cuda", ctx.device)
+        src = np.frombuffer(region, np.uint8) if region else np.zeros(0, np.uint8)
+        batch = DeviceBatch(src, ext, ctx.device)
+        nb = batch.n_blocks
+        self._pinned = 0
+        self._verify(batch, any(int(ext[b + 1]) > int(ext[b]) and
+                                region[int(ext[b + 1]) - 1] in (2, 3) for b in range(nb)))
+        fk, fpos = _pack(first_keys or [])
+        self.first_keys = torch.from_numpy(fk.copy()).to(dev)
+        self.first_pos = torch.from_numpy(fpos).to(dev)
+        self._first_key_bytes = int(fpos[-1])
+        self.bloom = None if bloom is None else torch.from_numpy(
+            np.frombuffer(bloom or b"\0", np.uint8).copy()).to(dev)
+        self.bloom_len = 0 if bloom is None else len(bloom)
+        self._own_bloom = self.bloom_len
+
+    def _verify(self, batch: DeviceBatch, has_codec: bool) -> None:
+        """The codec step where some block needs it, then one tpz_raw_verify."""
+        nb = self.n_blocks = batch.n_blocks
+        self.ext_host = batch.ext_host      # the stored extents: BlockMeta::offset + the meta offset
+        self.codec = None
+        if has_codec:
+            batch, st = decompress_batch(self.ctx, batch)
+            self.codec = st[:nb]
+        self.batch = batch
+        dev = torch.device("cuda", self.ctx.device)
+        self.status = torch.zeros(max(nb, 1), dtype=torch.uint8, device=dev)
+        self.crc = torch.zeros(max(nb, 1), dtype=torch.int32, device=dev)
+        self.ctx.raw_verify_ptrs(batch.src.data_ptr(), batch.ext.data_ptr(), nb, batch.src_bytes,
+                                 self.status.data_ptr(), self.crc.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+        # the status a reader of block i sees: the codec's Err wins over the check of its stub
+        if self.codec is not None:
+            self.status[:nb] = torch.where(self.codec != BLOCK_OK, self.codec, self.status[:nb])
+
+    @classmethod
+    def from_resident(cls, ctx: Context, image: torch.Tensor, ext: torch.Tensor,
+                      first_keys: torch.Tensor, first_pos: torch.Tensor,
+                      filter_view: torch.Tensor | None, filter_len: int,
+                      has_codec: bool) -> "RawTable":
+        """The same object over a file image that already lies in HBM (open_images): the
+        arguments are DeviceTable.from_resident's. Nothing is uploaded and nothing decoded: the
+        table pins the image and adds its status and CRC columns."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._pinned = int(image.numel())
+        self._verify(DeviceBatch(image, ext, ctx.device), has_codec)
+        self.first_keys, self.first_pos = first_keys, first_pos
+        self._first_key_bytes = int(first_keys.numel())
+        self.bloom = filter_view
+        self.bloom_len = 0 if filter_view is None else int(filter_len)
+        self._own_bloom = 0          # the filter lies in the image
+        return self
+
+    @property
+    def resident_bytes(self) -> int:
+        """The device bytes the table owns or pins: the encoded blocks (the image it pins, and
+        the codec step's output where it ran), the extents, the first-key positions, the status
+        and CRC columns, the first keys and a filter of its own."""
+        nb = self.n_blocks
+        blocks = self._pinned
+        if self._pinned == 0 or self.codec is not None:
+            blocks += int(self.batch.src_bytes)
+        cols = 8 * (nb + 1) * 2 + nb + 4 * nb + (nb if self.codec is not None else 0)
+        return blocks + cols + self._first_key_bytes + self._own_bloom
+
+    def _block_bytes(self, b: int) -> bytes:
+        lo, hi = int(self.batch.ext_host[b]), int(self.batch.ext_host[b + 1])
+        return self.batch.src[lo:hi].cpu().numpy().tobytes()
+
+    def block_error(self, b: int) -> Exception | None:
+        """The exception the reference's read_block raises for block b (None: Ok(Block))."""
+        st = int(self.status[b].cpu())
+        if st == BLOCK_OK:
+            return None
+        if self.codec is not None and int(self.codec[b].cpu()) != BLOCK_OK:
+            return _status_error(st, 0, 0)
+        raw = self._block_bytes(b)
+        expected = _be32(raw[-5:-1]) if len(raw) >= 5 else 0
+        return _status_error(st, expected, int(self.crc[b].cpu()) & 0xFFFFFFFF)
+
+    def last_key(self) -> bytes:
+        """init_samllest_biggest_key's biggest key (table.rs:145-149): the last block's bytes
+        read back and parsed on the host as the reference's iterator reads them
+        (Block.from_verified), with its panics."""
+        b = self.n_blocks - 1
+        if b < 0:
+            raise ReferencePanic("index out of bounds: the len is 0 but the index is 0")
+        err = self.block_error(b)
+        if err is not None:
+            raise err
+        it = BlockIterator.create_and_seek_to_first(Block.from_verified(self._block_bytes(b)))
+        it.seek_to_last()
+        if not it.is_valid():
+            raise ReferencePanic("assertion failed: iter.is_valid()")
+        return it.key()
+
+    def raw_table(self) -> _lib.RawTable:
+        return _lib.RawTable(self.first_keys.data_ptr(), self.first_pos.data_ptr(),
+                             self.batch.src.data_ptr(), self.batch.ext.data_ptr(), self.n_blocks,
+                             self.status.data_ptr(),
+                             self.bloom.data_ptr() if self.bloom is not None else None,
+                             self.bloom_len)
+
+    def seek_keys(self, keys: list[bytes]) -> dict:
+        """DeviceTable.seek_keys over the encoded blocks (tpz_raw_seek_keys)."""
+        dev = torch.device("cuda", self.ctx.device)
+        n = len(keys)
+        buf, pos = _pack(keys)
+        q = torch.from_numpy(buf.copy()).to(dev)
+        qp = torch.from_numpy(pos).to(dev)
+        out = {k: torch.empty(max(n, 1), dtype=t, device=dev) for k, t in
+               (("block", torch.int32), ("entry", torch.int32), ("status", torch.uint8),
+                ("valid", torch.uint8))}
+        self.ctx.raw_seek_keys_ptrs(self.raw_table(), q.data_ptr(), qp.data_ptr(), n,
+                                    out["block"].data_ptr(), out["entry"].data_ptr(),
+                                    out["status"].data_ptr(), out["valid"].data_ptr(),
+                                    torch.cuda.current_stream(dev).cuda_stream)
+        return {k: v[:n].cpu().numpy() for k, v in out.items()}
+
+    may_contain = DeviceTable.may_contain
+
+
 def _decode_region(ctx: Context, region: bytes, ext: np.ndarray) -> list:
     """Decode blocks [ext[i], ext[i+1]) of `region`: snappy and lz4 blocks first go through the
     device codec step (compress.rs:104-111), then one tpz_decode_blocks launch decodes the batch.
@@ -727,7 +864,7 @@ def _open_error(status: int, image: torch.Tensor) -> Exception:
 
 
 def open_images(ctx: Context, arena: torch.Tensor, spans, verify: bool = True,
-                strict: bool = True) -> list:
+                strict: bool = True, raw: bool = False) -> list:
     """SsTable::open (src/table.rs:91-112) for SST file images that already lie in HBM, without a
     host round trip: image i is arena[start : start + length] for (start, length) = spans[i], the
     whole file with its CRC trailer, as compact_task and flush_runs leave them. Starts are
@@ -740,7 +877,10 @@ def open_images(ctx: Context, arena: torch.Tensor, spans, verify: bool = True,
     `smallest_key`, `biggest_key` (init_samllest_biggest_key, :143-151), `size` and
     `block_meta_offset` set; the tables keep the arena and the shared arrays alive. A file that
     fails becomes the exception SsTable.open / FileObject.open raise for it: raised, the first in
-    file order, when `strict`; returned in its place otherwise."""
+    file order, when `strict`; returned in its place otherwise.
+
+    raw: every image opens as a RawTable (in place: the same parse, tpz_raw_verify instead of the
+    decode, no decoded columns), with the same attributes and the same errors."""
     spans = [(int(s), int(n)) for s, n in spans]
     end = 0
     for s, n in spans:
@@ -785,7 +925,7 @@ def open_images(ctx: Context, arena: torch.Tensor, spans, verify: bool = True,
             nb, b0, k0, k1 = int(row[6]), int(fb[i]) + i, int(fk[i]), int(fk[i + 1])
             boff, flen = int(row[4]), int(row[5])
             try:
-                t = DeviceTable.from_resident(
+                t = (RawTable if raw else DeviceTable).from_resident(
                     ctx, image, ext[b0:b0 + nb + 1], keys[k0:max(k1, k0 + 1)],
                     pos[b0:b0 + nb + 1],
                     None if boff == 2**64 - 1 else image[boff:boff + flen], flen,
