@@ -35,10 +35,11 @@ def block_of(c):
     return c.stream + b"\x02"
 
 
-def run_codec(ctx, blocks, src=None, src_bytes=None):
+def run_codec(ctx, blocks, src=None, src_bytes=None, claimed=False, check=True):
     """tpz_decompressed_sizes + prefix sum + tpz_decompress_blocks into an output filled with
     CANARY that has SLACK bytes after dst_ext[n]: (block outputs, statuses, ext, dst_ext). `src`:
-    a device tensor that already holds the batch at its start, passed with `src_bytes`."""
+    a device tensor that already holds the batch at its start, passed with `src_bytes`. `claimed`:
+    tpz_decompressed_sizes_claimed; `check`: what tpz_decompress_check must then return."""
     data, ext = batch_of(blocks)
     n = len(blocks)
     if src is None:
@@ -47,7 +48,8 @@ def run_codec(ctx, blocks, src=None, src_bytes=None):
     assert src_bytes <= src.numel()
     d_ext = torch.from_numpy(ext.view(np.int64).copy()).cuda()
     size = torch.empty(n, dtype=torch.int64, device="cuda")
-    ctx.decompressed_sizes_ptrs(src.data_ptr(), d_ext.data_ptr(), n, src_bytes, size.data_ptr())
+    ctx.decompressed_sizes_ptrs(src.data_ptr(), d_ext.data_ptr(), n, src_bytes, size.data_ptr(),
+                                claimed=claimed)
     dext = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
     torch.cumsum(size, 0, out=dext[1:])
     total = int(dext[-1])
@@ -55,7 +57,7 @@ def run_codec(ctx, blocks, src=None, src_bytes=None):
     st = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
     ctx.decompress_ptrs(src.data_ptr(), d_ext.data_ptr(), n, src_bytes, dst.data_ptr(),
                         dext.data_ptr(), st.data_ptr())
-    assert ctx.decompress_check()
+    assert ctx.decompress_check() == check
     torch.cuda.synchronize()
     host = dst.cpu().numpy()
     oext = dext.cpu().numpy()
