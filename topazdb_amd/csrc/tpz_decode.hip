@@ -33,7 +33,8 @@
 //  instruction). A regular block (every entry one key length and one value length, both >= 16,
 //  back to back) skips the table and the map on the slotted wave path: its ends and the copy's
 //  chunk -> entry index are closed forms of (n, KL, VL) (decode_block, copy_crc_piped<.., REG>);
-//  a wave computes that index once per (n, KL, VL) and keeps it, packed, in its idle entry table.
+//  a wave computes that index once per (n, KL, VL) and keeps it, packed, in its idle entry table
+//  (lengths that are multiples of 4: as four source offsets per chunk, one per output dword).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -101,6 +102,12 @@ static_assert(2 * kWaveMaxN + 1 <= (u32)kWaveTabSlots, "entry table");
 // timing build with the short table in the map too: a regular block uses neither, and the
 // general parse, which writes both, invalidates it)
 static_assert(kWaveTabSlots * 4 + 2 * kWaveMapLen >= kWave * 16, "index cache");
+// (the dword index of a geometry with 4-byte-multiple lengths takes 32 bytes per lane: the whole
+// entry table, no LDS added; the timing build's short table has no room and never holds one)
+constexpr bool kRegDwordFits = kWaveTabSlots * 4 >= kWave * 32;
+#ifndef TPZ_ABL_W20
+static_assert(kRegDwordFits && kWaveTabSlots * 4 == kWave * 32, "dword index cache");
+#endif
 constexpr int kWaveLds = kWaveTabBytes + kWavesPerWG * kSlotBytes;
 static_assert(kWaveLds <= 163840, "wave path LDS");
 
@@ -1097,6 +1104,7 @@ struct PWin {
   int d0, d1;
   bool act, cross;
   Gath ga, gn;
+  u32 a[4], g[8];    // the dword index (copy_crc_piped<.., DW>): four LDS addresses, their reads
 };
 // Windows w < K3 of copy_crc_piped<K3>: the key windows of a block with keys under 16 bytes (Zipf
 // keys), copy_fast3's chunk rule: entries j .. j + 3, a lost map race taken back, up to three
@@ -1187,6 +1195,24 @@ __device__ __forceinline__ u32 reg_pack(const RegForm& R, u32 w, u32 lane, u32 n
                    (cross ? (((x0 + (u32)d1 + kRegBias) & 0x1FFFu) << 13) | ((e0 - x0) << 26) : 16u << 26);
   return c < nch ? word : kRegNoChunk;
 }
+// The dword index: what the cache holds instead when KL and VL are multiples of 4 (reg_eligible).
+// Then every entry boundary of the stream falls on a dword of its chunk (m is 4, 8, 12 or 16), so
+// output dword k of chunk c is four whole bytes of one source, the chunk's own (4 k < m) or its
+// successor's: at f_k = (4 k < m ? A : B) + 4 k from db, A, B, m the fields of reg_pack's word.
+// Two words per lane and window, lo = f_0 | f_1 << 16, hi = f_2 | f_3 << 16 (each f_k < 2^13; the
+// sources' byte phases may differ: a key lies at 2 mod 4 from db, a value and the gap's bytes at
+// 0); no chunk c: both 0, and lo != 0 otherwise (f_0 = A >= 2). 32 bytes per lane: the whole entry
+// table (tests/test_regular_dword_index.py walks the shapes).
+__device__ __forceinline__ bool reg_eligible(u32 KL, u32 VL) { return ((KL | VL) & 3u) == 0; }
+__device__ __forceinline__ void reg_dwords(u32 word, u32& lo, u32& hi) {
+  const u32 A = word & 0x1FFFu, B = ((word >> 13) & 0x1FFFu) - kRegBias, m = (word >> 26) & 31u;
+  u32 f[4];
+#pragma unroll
+  for (u32 k = 0; k < 4; k++) f[k] = (4 * k < m ? A : B) + 4 * k;
+  const bool none = (int)word < 0;
+  lo = none ? 0u : f[0] | f[1] << 16;
+  hi = none ? 0u : f[2] | f[3] << 16;
+}
 // The geometry whose index the wave's cache holds, in one word (one register across the block
 // loop: with two the loop's SGPR spills went from 33 to 347). A regular block has n (6 + KL + VL) <=
 // 4329, so n >= 2 leaves KL, VL < 4096: n << 24 | VL << 12 | KL with n <= 113; n = 1 sets bit 31
@@ -1217,7 +1243,10 @@ struct RegWords<false> {};
 // REG: the block is regular (G) and the windows' sources, successors and crossings come from the
 // packed index rix (reg_pack: the wave's cache or built for this block) instead of the map, the
 // prefix max and the entry table (col, map, nk are not read).
-template <bool FLAT, u32 K3, bool REG = false>
+// DW: key and value lengths are multiples of 4, and rix and the table's second KiB hold the dword
+// index (reg_dwords): an output dword is four whole bytes of one source, one ds_read2_b32 and one
+// v_alignbyte; no second gather, no merge. (The fifth window keeps the closed form and merge_at.)
+template <bool FLAT, u32 K3, bool REG = false, bool DW = false>
 __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& col,
                                               const uint16_t* map, u32 nk, u32 tot, uint8_t* dst,
                                               const FlatOut& D, const uint8_t* win, int pb, u32 Pa,
@@ -1225,6 +1254,7 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
                                               const RegGeom G = RegGeom{0u, 0u, 0u, 0u},
                                               const u32x4v rix = u32x4v{0u, 0u, 0u, 0u}) {
   static_assert(!REG || (K3 == 0 && !FLAT), "the regular copy: slotted, no short keys");
+  static_assert(!DW || REG, "the dword index: regular blocks only");
   // (k3n <= K3, uniform: the windows that hold short keys; the others take the plain rule)
   const u32 lane = lane_id();
   FastWin F;
@@ -1255,6 +1285,20 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
     // (unpacked here, in stage B, not sunk between a window's store and the next one's gathers)
     asm volatile("" : "+v"(P.e0), "+v"(P.d0), "+v"(P.d1));
   };
+  // DW: a window's PWin holds a[k], the LDS address of the four source bytes of output dword k
+  // (the guard where there is no chunk: an index of zeros). One add per address, the window's
+  // address and db in its uniform term. Window w is unpacked one stage before its reads are
+  // issued (w0 in B, w1 in E, w2 in G, w3 in I) and pinned there: four addresses per window live
+  // at a time, not sixteen.
+  const u32 wlds = (u32)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)win;
+  auto dw_unpack = [&](PWin& P, u32 lo, u32 hi) {
+    const u32 base = lo ? wlds + G.db : wlds - (u32)kGuard;
+    P.a[0] = base + (lo & 0xFFFFu);
+    P.a[1] = base + (lo >> 16);
+    P.a[2] = base + (hi & 0xFFFFu);
+    P.a[3] = base + (hi >> 16);
+    asm volatile("" : "+v"(P.a[0]), "+v"(P.a[1]), "+v"(P.a[2]), "+v"(P.a[3]));
+  };
   // A: map reads, CRC data of step 0
   if constexpr (!REG) {
 #pragma unroll
@@ -1274,7 +1318,9 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   //    (REG: the packed index, unpacked)
   u32 cw[5];
   cw[0] = 0;
-  if (REG) {
+  if constexpr (DW) {
+    dw_unpack(W[0], rix.x, rix.y);
+  } else if (REG) {
     reg_unpack(W[0], rix.x);
     reg_unpack(W[1], rix.y);
     reg_unpack(W[2], rix.z);
@@ -1302,6 +1348,18 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   TPZ_SB();
   u32 rare = 0;
   auto gissue = [&](PWin& P, u32 w) {
+    if constexpr (DW) {
+      if (w < 4) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const __attribute__((address_space(3))) u32* q =
+              (const __attribute__((address_space(3))) u32*)(uintptr_t)(P.a[k] & ~3u);
+          P.g[2 * k] = q[0];
+          P.g[2 * k + 1] = q[1];
+        }
+        return;
+      }
+    }
     if constexpr (REG) {
       P.ga = gath_issue(win, P.d0);
       P.gn = gath_issue(win, P.d1);
@@ -1330,6 +1388,20 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   auto finish = [&](PWin& P, u32 w) {
     const u32 c = 64 * w + lane;
     const u32 x0 = 16 * c;
+    if constexpr (DW) {
+      if (w < 4) {
+        u32x4v acc;
+        asm volatile("" : "+v"(P.g[0]), "+v"(P.g[1]), "+v"(P.g[2]), "+v"(P.g[3]), "+v"(P.g[4]),
+                     "+v"(P.g[5]), "+v"(P.g[6]), "+v"(P.g[7]));
+        // (v_alignbyte_b32 shifts by its third operand's low two bits: the address itself will do)
+        acc.x = __builtin_amdgcn_alignbyte(P.g[1], P.g[0], P.a[0]);
+        acc.y = __builtin_amdgcn_alignbyte(P.g[3], P.g[2], P.a[1]);
+        acc.z = __builtin_amdgcn_alignbyte(P.g[5], P.g[4], P.a[2]);
+        acc.w = __builtin_amdgcn_alignbyte(P.g[7], P.g[6], P.a[3]);
+        __builtin_amdgcn_raw_buffer_store_b128(acc, F.out, x0, 0, 0);
+        return;
+      }
+    }
     if constexpr (REG) {
       uint4 acc = gath_finish(P.ga, P.d0);
       const uint4 nx = gath_finish(P.gn, P.d1);
@@ -1362,6 +1434,11 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   crc = look_xor(LK);
   LK = look_issue(tab, dB, crc);
   dA = dread(2);
+  u32x4v rix2;     // DW: the index words of windows 2 and 3, read here, used in G and I
+  if constexpr (DW) {
+    dw_unpack(W[1], rix.z, rix.w);
+    rix2 = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const uint8_t*>(col.t) + 1024 + 16 * lane);
+  }
   cA = comb_use<3>(cA, cl);
   cl = comb_issue<4>(tab, cA);
   TPZ_SB();
@@ -1374,6 +1451,7 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   crc = look_xor(LK);
   LK = look_issue(tab, dA, crc);
   dB = dread(3);
+  if constexpr (DW) dw_unpack(W[2], rix2.x, rix2.y);
   cA = comb_use<5>(cA, cl);
   comb_finish(tab, o, pd, cA, want);
   TPZ_SB();
@@ -1384,6 +1462,7 @@ __device__ __forceinline__ u32 copy_crc_piped(const u32* tab, const ColSmall& co
   crc = look_xor(LK);
   LK = look_issue(tab, dB, crc);
   dA = dread(4);
+  if constexpr (DW) dw_unpack(W[3], rix2.z, rix2.w);
   TPZ_SB();
   finish(W[2], 2);
   gissue(W[3], 3);
@@ -1555,21 +1634,39 @@ __device__ __forceinline__ void decode_block(const u32* tab, uint8_t* win, const
         // whatever they hold, and used only on a hit: the read's round trip overlaps the ends
         // store and crc_prepare. Read with the header, before the test, the 4k copy ran 0.1-0.4 %
         // faster and zipf batches, which never use it, 0.1-0.5 % slower: profiles/regcache/.)
+        // A geometry whose lengths are multiples of 4 keeps the dword index instead (reg_dwords):
+        // windows 0 and 1 in the first KiB of the table, 2 and 3 in the second, 16 bytes per lane
+        // each. Which one the words are follows from the key's geometry (uniform: no new state).
         const u32 key = reg_key(n, KL, VL);
+        const bool dw = kRegDwordFits && reg_eligible(KL, VL);
         rix.v = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const uint8_t*>(col.t) + 16 * lane);
         if (*rk != key) {
           const RegForm R(n, KL, VL);
           const u32 nch = (vs + vc + 15) >> 4;
           // (a loop, not unrolled, and read back: a miss is rare and its code stays small)
 #pragma nounroll
-          for (u32 w = 0; w < 4; w++) col.t[4 * lane + w] = reg_pack(R, w, lane, nch);
+          for (u32 w = 0; w < 4; w++) {
+            const u32 word = reg_pack(R, w, lane, nch);
+            if (dw) {
+              u32 lo, hi;
+              reg_dwords(word, lo, hi);
+              col.t[256 * (w >> 1) + 4 * lane + 2 * (w & 1)] = lo;
+              col.t[256 * (w >> 1) + 4 * lane + 2 * (w & 1) + 1] = hi;
+            } else {
+              col.t[4 * lane + w] = word;
+            }
+          }
           rix.v = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const uint8_t*>(col.t) + 16 * lane);
           *rk = key;
         }
         __builtin_amdgcn_wave_barrier();
         const u32 k = crc_prepare(win, a0, P);
         fin.on = false;     // the previous block's combine runs in the copy, before pd is reused
-        const u32 lc = copy_crc_piped<false, 0u, true>(
+        const u32 lc = dw ? copy_crc_piped<false, 0u, true, true>(
+            tab, *reinterpret_cast<const ColSmall*>(&col), reinterpret_cast<const uint16_t*>(map),
+            2 * n, vs + vc, o.data + slot_base(ext_b, b), fo, win, pb, P + k, o, pd, 0u,
+            RegGeom{n, KL, VL, db}, rix.v)
+                          : copy_crc_piped<false, 0u, true>(
             tab, *reinterpret_cast<const ColSmall*>(&col), reinterpret_cast<const uint16_t*>(map),
             2 * n, vs + vc, o.data + slot_base(ext_b, b), fo, win, pb, P + k, o, pd, 0u,
             RegGeom{n, KL, VL, db}, rix.v);
